@@ -16,6 +16,12 @@ also produces what ``scores.argmax()`` returns for the WHOLE sequence: the shard
 stream) are resident in HBM before the timed region; a time-based preheat runs
 before the counted warm-up.  Rank 0 prints ONE JSON line.
 
+A plain run sets up, warms up, times the K steps and prints the line (headline figure, the
+roofline of the timed kernels).  `--full` adds what takes runs of its own after the timed
+region: the reductions and fused scans on the last step's data, the sustained clock, the
+merges, end to end, configs[0] / [2] / [4] and the CPU baseline.  `--dump-outputs DIR` writes
+what the last timed step computed (a fixed sample of the score matrix) as DIR/<name>.npy.
+
 PyTorch is plumbing only (device buffers, stream, process group); every timed
 kernel is the hand-written HIP code behind include/lightmotif_hip.h.
 """
@@ -41,7 +47,7 @@ sys.path.insert(0, str(ROOT))
 import lightmotif_amd as lm  # noqa: E402
 from lightmotif_amd import distributed as D  # noqa: E402
 
-HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
+HBM_PEAK_GBS = 8000.0  # MI355X: HBM3E 8.0 TB/s spec
 BYTES_PER_POS = 5      # 1 B symbol read + 4 B f32 score written
 COLS = 32
 # Secondary ceiling: every position gathers M f32 weights from LDS, 4*M bytes at
@@ -109,6 +115,70 @@ def emit(obj: dict) -> None:
     out = _JSON_OUT or sys.stdout
     out.write(json.dumps(obj) + "\n")
     out.flush()
+
+
+# --dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy in float32 / float64.  The score matrix
+# of a 1 Gbp step is 4 GB, so a fixed sample of its rows is written: 2^17 rows over all ranks, the same rows for the same
+# arguments in every run, as the f32 scores of their scored positions + those positions (f64), ~48 MB; the hit lists of
+# --config c3 at most DUMP_HITS hits.
+DUMP_ROWS = 1 << 17
+DUMP_BLOCK = 1024
+DUMP_HITS = 1_500_000
+
+
+def dump_row_ranges(rows: int, budget: int, block: int = DUMP_BLOCK, seed: int = 0x5EED0004) -> list:
+    """Row ranges [a, b) of a `rows`-row matrix that --dump-outputs writes: every row when there are at most `budget`,
+    else the first and the last `block` rows and `budget // block - 2` whole blocks between them at seeded random places
+    (ascending, disjoint)."""
+    if rows <= budget:
+        return [(0, rows)]
+    nb = budget // block
+    assert nb >= 2, (budget, block)
+    inner = np.random.default_rng(seed).choice(rows // block - 2, nb - 2, replace=False) + 1
+    return [(0, block)] + [(int(k) * block, (int(k) + 1) * block) for k in np.sort(inner)] + [(rows - block, rows)]
+
+
+def dump_scores(dirpath: str, scores_h, rows: int, row0: int, total_rows: int, total_length: int, m: int, world: int,
+                rank: int, sharded: bool, merged) -> None:
+    """The resident StripedScores after the last timed step (the rank's row shard), sampled rows in row-major order:
+    `scores[_rank<r>].npy` the f32 score of every scored position in them, `score_positions[_rank<r>].npy` those sequence
+    positions (f64; cell (row, col) of the striped matrix is position col * total_rows + row).  Only the L - M + 1
+    positions a motif window fits in are scores (scores.rs); the cells past them read the wrap / padding rows and are left
+    out.  A sharded step's merged argmax as `argmax.npy` = [row, col, value] (f64; empty when the matrix has no maximum),
+    written by rank 0."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    ranges = dump_row_ranges(rows, max(DUMP_ROWS // world, 2 * DUMP_BLOCK))
+    sample = np.concatenate([scores_h.rows_matrix(a, b)[:, :COLS] for a, b in ranges]).astype(np.float32, copy=False)
+    index = np.concatenate([np.arange(a, b, dtype=np.int64) for a, b in ranges]) + row0
+    pos = np.arange(COLS, dtype=np.int64)[None, :] * total_rows + index[:, None]
+    keep = pos < total_length - m + 1
+    suffix = "" if world == 1 else f"_rank{rank}"
+    np.save(d / f"scores{suffix}.npy", np.ascontiguousarray(sample[keep]))
+    np.save(d / f"score_positions{suffix}.npy", pos[keep].astype(np.float64))
+    if sharded and rank == 0:
+        np.save(d / "argmax.npy", np.zeros(0) if merged is None else
+                np.array([merged[0][0], merged[0][1], merged[1]], dtype=np.float64))
+
+
+def dump_hits(dirpath: str, res) -> None:
+    """--config c3: the per-motif hit lists of the last timed batch, flattened in motif order: `hits_per_motif.npy` (f64
+    counts, every motif), `hits_motif.npy` / `hits_coords.npy` (f64 motif index, (row, col)) and `hits_scores.npy` (f32);
+    beyond DUMP_HITS hits a seeded sample of them (in order)."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    pairs = list(res)
+    counts = np.array([len(c) for c, _ in pairs], dtype=np.int64)
+    motif = np.repeat(np.arange(len(pairs), dtype=np.int64), counts)
+    coords = np.concatenate([np.asarray(c, dtype=np.int64).reshape(-1, 2) for c, _ in pairs] + [np.zeros((0, 2), np.int64)])
+    values = np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for _, v in pairs] + [np.zeros(0, np.float32)])
+    if len(motif) > DUMP_HITS:
+        keep = np.sort(np.random.default_rng(0x5EED0005).choice(len(motif), DUMP_HITS, replace=False))
+        motif, coords, values = motif[keep], coords[keep], values[keep]
+    np.save(d / "hits_per_motif.npy", counts.astype(np.float64))
+    np.save(d / "hits_motif.npy", motif.astype(np.float64))
+    np.save(d / "hits_coords.npy", coords.astype(np.float64))
+    np.save(d / "hits_scores.npy", values)
 
 
 def synth_pssm(m: int, seed: int = 0x5EED0002) -> lm.ScoringMatrix:
@@ -443,12 +513,15 @@ def main_c3(args) -> None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    am = D.scan_argmax_batch_sharded(pli, pssms, seq, device=coll_dev, parts=parts)
-    t1 = time.perf_counter()
-    for _ in range(max(args.steps // 2, 1)):
+    if args.dump_outputs and rank == 0:
+        dump_hits(args.dump_outputs, res)
+    if args.full:
         am = D.scan_argmax_batch_sharded(pli, pssms, seq, device=coll_dev, parts=parts)
-    barrier()
-    am_s = (time.perf_counter() - t1) / max(args.steps // 2, 1)
+        t1 = time.perf_counter()
+        for _ in range(max(args.steps // 2, 1)):
+            am = D.scan_argmax_batch_sharded(pli, pssms, seq, device=coll_dev, parts=parts)
+        barrier()
+        am_s = (time.perf_counter() - t1) / max(args.steps // 2, 1)
     if rank != 0:
         if world > 1:
             dist.barrier()
@@ -471,15 +544,16 @@ def main_c3(args) -> None:
                    "motifs_per_rank": [len(p) for p in parts]},
         "extras": {"hits_total": int(sum(len(c) for c, _ in res)),
                    "motifs_unreachable_at_p": len(unreachable),
-                   "scanned_Gcell_s": round(scanned_cells * args.steps / elapsed / 1e9, 1),
-                   "fused_argmax_ms": round(am_s * 1e3, 3),
-                   "fused_argmax_Gcell_s": round(cells / am_s / 1e9, 1),
-                   "argmax_found": int(sum(a is not None for a in am))},
+                   "scanned_Gcell_s": round(scanned_cells * args.steps / elapsed / 1e9, 1)},
         "roofline": lds_roofline(c3["lds_bytes"] * args.steps, elapsed, C3_LDS_MODEL),
         "roofline_note": "LDS-gather-bound scans over a cache-resident sequence: the PMC-based LDS / VALU utilisation "
                          "per kernel is in profiles/r02_c3_record.md; no HBM fraction applies",
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["extras"].update({"fused_argmax_ms": round(am_s * 1e3, 3),
+                              "fused_argmax_Gcell_s": round(cells / am_s / 1e9, 1),
+                              "argmax_found": int(sum(a is not None for a in am))})
+    if args.full and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_c3(shard, rows, length, max_m, pssms, res, am, args.cpu_seconds)
     emit(out)
     if world > 1:
@@ -880,8 +954,14 @@ def main() -> None:
                     help="c2 (default): the headline score() of configs[1] / configs[3]; c3: the JASPAR batch of configs[2]")
     ap.add_argument("--motifs", type=int, default=0, help="c3: use only the first N matrices (development)")
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
-    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default: 200; c3: 10)")
+    ap.add_argument("--warmup", type=int, default=None, help="counted warm-up steps (default: 50; c3: 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need, after the timed region: the extras (reductions, "
+                         "fused scans, sustained clock, merges, end-to-end, configs[0] / [2] / [4]) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64, "
+                         "a fixed seeded sample of the score matrix, 64 MB at most in all)")
     ap.add_argument("--length", type=int, default=1_000_000_000, help="positions per GPU")
     ap.add_argument("--motif-len", type=int, default=20)
     ap.add_argument("--preheat-ms", type=float, default=300.0,
@@ -906,16 +986,20 @@ def main() -> None:
     ap.add_argument("--comm-timeout-s", type=float, default=120.0,
                     help="N > 1: bound on every collective's wait (process group and the C ABI's communicator)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip extras.configs (configs[0], [2], [4] of BASELINE.json after the timed region)")
+                    help="with --full: skip extras.configs (configs[0], [2], [4] of BASELINE.json after the timed region)")
     args = ap.parse_args()
+    if args.steps is None:
+        args.steps = 10 if args.config == "c3" else 200
+    if args.warmup is None:
+        args.warmup = 3 if args.config == "c3" else 50
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:    # no launcher: become one (before stdout is set aside)
         if not args.single_device and torch.cuda.device_count() < args.gpus:
             raise SystemExit(f"--gpus {args.gpus}: this node shows {torch.cuda.device_count()} GPU(s)")
         self_launch(args.gpus)                              # does not return
     claim_stdout()
     if args.config == "c3":
-        if args.steps == 200 and args.warmup == 50:
-            args.steps, args.warmup = 10, 3
         return main_c3(args)
 
     world, rank, local_rank, dev, coll_dev, launch_note = init_ranks(args)
@@ -1088,75 +1172,80 @@ def main() -> None:
     else:
         by_rank = [mine]
 
-    # --- reductions / merge on the last step's matrix (outside the timed region; "extras") --------
-    def timed(fn, reps=5, warm=0):
-        best, out = None, None
-        # the fused scans are quoted in steady state: the first ~60 calls of a process (or behind a pause of the device)
-        # take 0.30-0.33 ms where later ones take 0.27 -- host-side pools filling, then the clock governor
-        # (tools/scan_kernel_timer_check.py, profiles/r05_fused_call_warmup.txt)
-        for _ in range(warm):
-            fn()
-        for _ in range(reps):
-            torch.cuda.synchronize()
-            t = time.perf_counter()
-            out = fn()
-            torch.cuda.synchronize()
-            dt = (time.perf_counter() - t) * 1e3
-            best = dt if best is None else min(best, dt)
-        return best, out
+    if args.dump_outputs:
+        dump_scores(args.dump_outputs, scores_h, rows, row0, total_rows, total_length, m, world, rank, sharded, merged)
 
-    # The shader clock each kind of call sustains: a second thread runs lm_hip_device_clock_mhz windows (one mostly-sleeping
-    # wavefront on a stream of its own) while this one repeats the call, after the timed region.  The part clocks to its power budget, so every LDS / VALU fraction below is also
-    # quoted at this clock, not only at the 2.4 GHz of the data sheet.
-    def sustained_clock(fn, seconds=0.25):
-        mhz, beside_ms, alone_ms = pli.sustained_clock_mhz(fn, seconds)
-        # a probe that slows what it measures reports the clock of something else: dropped (None) beyond 15 %
-        return (mhz if mhz and beside_ms <= 1.15 * alone_ms else None), beside_ms
+    # --- --full only: reductions / merge on the last step's matrix (outside the timed region; "extras") -----
+    store_mhz, store_clock_ms, c3_sharded = None, None, None
+    if args.full:
+        def timed(fn, reps=5, warm=0):
+            best, out = None, None
+            # the fused scans are quoted in steady state: the first ~60 calls of a process (or behind a pause of the device)
+            # take 0.30-0.33 ms where later ones take 0.27 -- host-side pools filling, then the clock governor
+            # (tools/scan_kernel_timer_check.py, profiles/r05_fused_call_warmup.txt)
+            for _ in range(warm):
+                fn()
+            for _ in range(reps):
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                out = fn()
+                torch.cuda.synchronize()
+                dt = (time.perf_counter() - t) * 1e3
+                best = dt if best is None else min(best, dt)
+            return best, out
 
-    store_mhz, store_clock_ms = sustained_clock(lambda: pli.score_into(pssm, seq, scores_h))
+        # The shader clock each kind of call sustains: a second thread runs lm_hip_device_clock_mhz windows (one mostly-sleeping
+        # wavefront on a stream of its own) while this one repeats the call, after the timed region.  The part clocks to its power budget, so every LDS / VALU fraction below is also
+        # quoted at this clock, not only at the 2.4 GHz of the data sheet.
+        def sustained_clock(fn, seconds=0.25):
+            mhz, beside_ms, alone_ms = pli.sustained_clock_mhz(fn, seconds)
+            # a probe that slows what it measures reports the clock of something else: dropped (None) beyond 15 %
+            return (mhz if mhz and beside_ms <= 1.15 * alone_ms else None), beside_ms
 
-    sc_ptr = scores_h.data_ptr
-    am_ms, am = timed(lambda: pli.argmax_dptr(sc_ptr, rows, COLS, COLS, first_cell_rule=rank == 0))
-    fam_ms, fam = timed(lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS,
-                                                      m - 1, total_length, 0, rows, first_cell_rule=rank == 0), warm=60)
-    fam_kernel, fam_info = pli.last_kernel, pli.last_scan_info
-    assert am == fam, (am, fam)
-    mg_ms, best = timed(lambda: D.merge_argmax(am, row0, device=coll_dev))
-    if merged is not None:
-        assert merged == best, ("per-step merge differs from the merge of the materialised argmax", merged, best)
-    # threshold ~ the p = 1e-5 tail the CLI defaults to (main.rs:487): estimated from a sample
-    sample = torch.from_numpy(scores_h.rows_matrix(0, min(rows, 1 << 18))[:, :COLS].reshape(-1))
-    thr_t = float(torch.quantile(sample[torch.isfinite(sample)][:8_000_000].float(), 1 - 1e-5))
-    if world > 1:   # one threshold for the whole job: rank 0's estimate
-        tt = torch.tensor([thr_t], dtype=torch.float64, device=coll_dev)
-        dist.broadcast(tt, src=0)
-        thr_t = float(tt.item())
-    th_ms, hits = timed(lambda: pli.threshold_dptr(sc_ptr, rows, COLS, COLS, thr_t), reps=5)
-    fth_ms, fhits = timed(lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS,
-                                                          m - 1, total_length, 0, rows, thr_t), reps=5, warm=60)
-    fth_kernel, fth_info = pli.last_kernel, pli.last_scan_info
-    assert np.array_equal(hits, fhits[0]), "fused threshold differs from materialised threshold"
-    fam_kms = scan_kernel_ms(pli, lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
-                                                                 total_length, 0, rows))
-    fth_phases = {}
-    fth_kms = scan_kernel_ms(pli, lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
-                                                                    total_length, 0, rows, thr_t), phases=fth_phases)
-    fam_mhz, _ = sustained_clock(lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
-                                                               total_length, 0, rows, first_cell_rule=rank == 0))
-    fth_mhz, _ = sustained_clock(lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
-                                                                  total_length, 0, rows, thr_t))
-    # Scanner::max as the reference walks it (scan.rs:200-249; csrc/scanmax.hip), a fresh scanner at the same threshold
-    smax_ms, smax = timed(lambda: lm.Scanner(pssm, seq, threshold=thr_t).max(), reps=5, warm=3)
-    smax_kernel = pli.last_kernel
-    mt_ms, all_hits = timed(lambda: (comm.merge_threshold(hits, row0) if comm is not None else
-                                     D.merge_threshold(hits, row0, device=coll_dev)), reps=3)
-    # the same list through the other transport (one timed merge per variant of the step)
-    mt_torch_ms, all_hits_t = (timed(lambda: D.merge_threshold(hits, row0, device=coll_dev), reps=3)
-                               if comm is not None else (mt_ms, all_hits))
-    assert np.array_equal(np.asarray(all_hits), np.asarray(all_hits_t)), "merge_threshold: the two transports disagree"
-    # configs[2] with the motif list sharded over the ranks (every rank takes part)
-    c3_sharded = (c3_leg(pli, dev, coll_dev, world, rank, reps=3)
-                  if world > 1 and not args.no_extras and (ROOT / "tests" / "golden" / "JASPAR2024.pwm.gz").exists() else None)
+        store_mhz, store_clock_ms = sustained_clock(lambda: pli.score_into(pssm, seq, scores_h))
+
+        sc_ptr = scores_h.data_ptr
+        am_ms, am = timed(lambda: pli.argmax_dptr(sc_ptr, rows, COLS, COLS, first_cell_rule=rank == 0))
+        fam_ms, fam = timed(lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS,
+                                                          m - 1, total_length, 0, rows, first_cell_rule=rank == 0), warm=60)
+        fam_kernel, fam_info = pli.last_kernel, pli.last_scan_info
+        assert am == fam, (am, fam)
+        mg_ms, best = timed(lambda: D.merge_argmax(am, row0, device=coll_dev))
+        if merged is not None:
+            assert merged == best, ("per-step merge differs from the merge of the materialised argmax", merged, best)
+        # threshold ~ the p = 1e-5 tail the CLI defaults to (main.rs:487): estimated from a sample
+        sample = torch.from_numpy(scores_h.rows_matrix(0, min(rows, 1 << 18))[:, :COLS].reshape(-1))
+        thr_t = float(torch.quantile(sample[torch.isfinite(sample)][:8_000_000].float(), 1 - 1e-5))
+        if world > 1:   # one threshold for the whole job: rank 0's estimate
+            tt = torch.tensor([thr_t], dtype=torch.float64, device=coll_dev)
+            dist.broadcast(tt, src=0)
+            thr_t = float(tt.item())
+        th_ms, hits = timed(lambda: pli.threshold_dptr(sc_ptr, rows, COLS, COLS, thr_t), reps=5)
+        fth_ms, fhits = timed(lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS,
+                                                              m - 1, total_length, 0, rows, thr_t), reps=5, warm=60)
+        fth_kernel, fth_info = pli.last_kernel, pli.last_scan_info
+        assert np.array_equal(hits, fhits[0]), "fused threshold differs from materialised threshold"
+        fam_kms = scan_kernel_ms(pli, lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
+                                                                     total_length, 0, rows))
+        fth_phases = {}
+        fth_kms = scan_kernel_ms(pli, lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
+                                                                        total_length, 0, rows, thr_t), phases=fth_phases)
+        fam_mhz, _ = sustained_clock(lambda: pli.score_argmax_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
+                                                                   total_length, 0, rows, first_cell_rule=rank == 0))
+        fth_mhz, _ = sustained_clock(lambda: pli.score_threshold_dptr(pssm, shard.data_ptr(), rows + m - 1, COLS, COLS, m - 1,
+                                                                      total_length, 0, rows, thr_t))
+        # Scanner::max as the reference walks it (scan.rs:200-249; csrc/scanmax.hip), a fresh scanner at the same threshold
+        smax_ms, smax = timed(lambda: lm.Scanner(pssm, seq, threshold=thr_t).max(), reps=5, warm=3)
+        smax_kernel = pli.last_kernel
+        mt_ms, all_hits = timed(lambda: (comm.merge_threshold(hits, row0) if comm is not None else
+                                         D.merge_threshold(hits, row0, device=coll_dev)), reps=3)
+        # the same list through the other transport (one timed merge per variant of the step)
+        mt_torch_ms, all_hits_t = (timed(lambda: D.merge_threshold(hits, row0, device=coll_dev), reps=3)
+                                   if comm is not None else (mt_ms, all_hits))
+        assert np.array_equal(np.asarray(all_hits), np.asarray(all_hits_t)), "merge_threshold: the two transports disagree"
+        # configs[2] with the motif list sharded over the ranks (every rank takes part)
+        c3_sharded = (c3_leg(pli, dev, coll_dev, world, rank, reps=3)
+                      if world > 1 and not args.no_extras and (ROOT / "tests" / "golden" / "JASPAR2024.pwm.gz").exists() else None)
 
     if rank != 0:
         if comm is not None:
@@ -1235,24 +1324,10 @@ def main() -> None:
             "lds_note": f"secondary ceiling: {4 * m} B of LDS gathers per position against 256 B/clk/CU x 256 CUs x 2.4 GHz",
             **at_sustained_clock(store_mhz, lds_bytes_per_s, m * rows * COLS / (kernel_avg_ms * 1e-3),
                                  f"{m} v_add_f32 per position (the algorithm's adds alone)"),
-            "clock_pass_ms_per_launch": round(store_clock_ms, 4),
+            **({"clock_pass_ms_per_launch": round(store_clock_ms, 4)} if store_clock_ms is not None else {}),
         },
         "extras": {
-            "argmax_ms": round(am_ms, 4), "fused_score_argmax_ms": round(fam_ms, 4),
-            "fused_score_argmax_gpos": round(rows * COLS / fam_ms / 1e6, 1),
-            "merge_argmax_ms": round(mg_ms, 4), "threshold_ms": round(th_ms, 4),
-            "fused_score_threshold_ms": round(fth_ms, 4), "threshold_t": round(thr_t, 4),
-            "merge_threshold_ms": round(mt_ms, 4),
-            "scanner_max_ms": round(smax_ms, 4), "scanner_max_kernel": smax_kernel,
-            "scanner_max": None if smax is None else [int(smax.position), round(float(smax.score), 4)],
-            "threshold_hits": int(len(all_hits)), "argmax_global": [int(best[0][0]), int(best[0][1])],
             "kernel_ms_min": round(min(kernel_ms), 4), "kernel_ms_max": round(max(kernel_ms), 4),
-            # SURVEY 8(d): the fused forms never write the score matrix -- priced against the LDS-gather ceiling (the pair
-            # table's (M | 3) + 1 bytes per position), the 1 B per position of HBM reads beside it
-            "fused_score_argmax": fused_roofline(fam_ms, rows, m, fam_kernel, fam_mhz, fam_kms, fam_info),
-            "fused_score_threshold": {**fused_roofline(fth_ms, rows, m, fth_kernel, fth_mhz, fth_kms, fth_info),
-                                      **({"phases": fth_phases} if fth_phases else {})},
-            "merge_threshold_ms_torch": round(mt_torch_ms, 4),
             "merge_us": (None if not rank_merge else
                          {"p50": round(float(np.median([x[0] for x in rank_merge])), 1),
                           "max": round(max(x[1] for x in rank_merge), 1),
@@ -1261,16 +1336,34 @@ def main() -> None:
                                   "median of the ranks' medians, maximum over ranks and steps"
                                   + ("; pipelined -- the next step's enqueue lies inside" if pipelined else "")}),
         },
+        "cpu_baseline": None,
     }
     if invalid:
         out["invalid"] = invalid
-    if world == 1 and not args.no_extras:
+    if args.full:
+        out["extras"].update({
+            "argmax_ms": round(am_ms, 4), "fused_score_argmax_ms": round(fam_ms, 4),
+            "fused_score_argmax_gpos": round(rows * COLS / fam_ms / 1e6, 1),
+            "merge_argmax_ms": round(mg_ms, 4), "threshold_ms": round(th_ms, 4),
+            "fused_score_threshold_ms": round(fth_ms, 4), "threshold_t": round(thr_t, 4),
+            "merge_threshold_ms": round(mt_ms, 4),
+            "scanner_max_ms": round(smax_ms, 4), "scanner_max_kernel": smax_kernel,
+            "scanner_max": None if smax is None else [int(smax.position), round(float(smax.score), 4)],
+            "threshold_hits": int(len(all_hits)), "argmax_global": [int(best[0][0]), int(best[0][1])],
+            # SURVEY 8(d): the fused forms never write the score matrix -- priced against the LDS-gather ceiling (the pair
+            # table's (M | 3) + 1 bytes per position), the 1 B per position of HBM reads beside it
+            "fused_score_argmax": fused_roofline(fam_ms, rows, m, fam_kernel, fam_mhz, fam_kms, fam_info),
+            "fused_score_threshold": {**fused_roofline(fth_ms, rows, m, fth_kernel, fth_mhz, fth_kms, fth_info),
+                                      **({"phases": fth_phases} if fth_phases else {})},
+            "merge_threshold_ms_torch": round(mt_torch_ms, 4),
+        })
+    if args.full and world == 1 and not args.no_extras:
         out["extras"]["end_to_end"] = end_to_end(shard, rows, m, total_length, pssm, scores_h, dev)
         out["extras"]["configs"] = secondary_configs(pli, dev)
         out["extras"]["crossover_positions"] = host_pointer_bench().crossover_positions()
     elif c3_sharded is not None:
         out["extras"]["configs"] = {"c3": c3_sharded}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         # rank 0's host cores, whatever N (the other ranks wait at the closing barrier): the sample is the head of
         # rank 0's shard; a window that reaches the shard's end needs the halo rows the exchange delivered
         srows = min(rows, max(args.cpu_sample // COLS, 1))
@@ -1278,8 +1371,6 @@ def main() -> None:
         gpu_sample = scores_h.rows_matrix(0, srows)
         out["cpu_baseline"] = cpu_baseline(seq_sample, total_length, pssm.data, gpu_sample,
                                            args.cpu_seconds)
-    else:
-        out["cpu_baseline"] = None
     emit(out)
     if comm is not None:
         comm.close()

@@ -92,25 +92,41 @@ for name, (res, args) in _ffi.SIGNATURES.items():
     print(name, file=sys.stderr, flush=True)          # the last name printed is the one that crashed, if any does
     st = getattr(L, name)(*vals)
     out[name] = [st, _ffi.last_error() if st else ""]
-print(json.dumps(out))
+# the usable device ordinals (the zero above is one of them on a GPU machine), a bind to an ordinal that is none, and -1
+n, ords = C.c_int(0), []
+L.lm_hip_device_count(C.byref(n))
+for i in range(n.value):
+    o = C.c_int(-1)
+    L.lm_hip_device_ordinal(i, C.byref(o))
+    ords.append(o.value)
+bad = L.lm_hip_host_bind_thread(1 << 20)
+bad = [bad, _ffi.last_error() if bad else ""]
+print(json.dumps({"calls": out, "ordinals": ords, "bind_unusable": bad, "bind_auto": L.lm_hip_host_bind_thread(-1)}))
 """
 
 
 def test_null_arguments_are_a_status_not_a_crash():
     """SURVEY 8(b) error conventions: misuse comes back as a status with a message, never as a fault or an exception
     across the ABI.  Every int-returning entry point is called with null handles / pointers and zero sizes (before
-    any device work, so this runs without a GPU); `*_destroy(NULL)` is a no-op like free(NULL)."""
+    any device work, so this runs without a GPU); `*_destroy(NULL)` is a no-op like free(NULL).  The one zero that is not
+    misuse everywhere: `lm_hip_host_bind_thread(0)` names ordinal 0, a usable device on a GPU machine."""
     import json
     import sys
     r = subprocess.run([sys.executable, "-c", NULL_CALLS, str(ROOT)], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, "crashed in " + (r.stderr.strip().splitlines() or ["?"])[-1]
-    got = json.loads(r.stdout.strip().splitlines()[-1])
+    res = json.loads(r.stdout.strip().splitlines()[-1])
+    got = res["calls"]
     assert len(got) >= 65
     for name, (st, msg) in got.items():
         if name.endswith("_destroy") or name in ("lm_hip_host_spread_lanes", "lm_hip_host_reuse_scores", "lm_hip_host_set_crossover"):   # (plain switches: nothing to misuse)
             assert st == 0, (name, st, msg)
+        elif name == "lm_hip_host_bind_thread" and 0 in res["ordinals"]:   # ordinal 0 is a usable device here
+            assert st == 0, (name, st, msg)
         else:
             assert st != 0 and msg, (name, st, msg)
+    st, msg = res["bind_unusable"]                   # an ordinal that is no usable device: a status on every machine
+    assert st != 0 and msg, ("lm_hip_host_bind_thread(1 << 20)", st, msg)
+    assert res["bind_auto"] == 0                     # -1: back to the automatic placement
 
 
 def test_header_is_plain_c99_and_links_from_c(tmp_path):

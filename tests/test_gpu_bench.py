@@ -33,7 +33,7 @@ def test_two_ranks_without_a_launcher():
     """`python bench.py --gpus 2 ...` with no WORLD_SIZE in the environment re-executes itself under
     torch.distributed.run and prints one line for a 2-rank job."""
     out = run_bench("--gpus", "2", "--single-device", "--dist-backend", "gloo", "--steps", "3", "--warmup", "1",
-                    "--length", "20000000", "--preheat-ms", "20")
+                    "--length", "20000000", "--preheat-ms", "20", "--full")
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["scaling"] == "weak"
     cfg = out["config"]
     assert cfg["parallelism"] == "row-shard x2" and cfg["halo_verified"] is True
@@ -42,7 +42,7 @@ def test_two_ranks_without_a_launcher():
     assert out["value"] > 0 and out["roofline"]["kernel"].startswith("score_c32<20")
     # the merged argmax of the 40 Mbp job is the same cell a single process finds on the whole sequence
     whole = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--length", "40000000", "--preheat-ms", "20",
-                      "--no-cpu-baseline", "--no-extras")
+                      "--full", "--no-cpu-baseline", "--no-extras")
     assert out["extras"]["argmax_global"] == whole["extras"]["argmax_global"]
     assert out["extras"]["threshold_hits"] > 0
     # what the first real N > 1 run will be read by: a CPU leg on rank 0, the per-rank kernel spread, the aggregate rate as
@@ -71,13 +71,14 @@ def test_eight_ranks_rehearsed_on_one_device():
     on cuda:0 over gloo -- 8 row shards + halos, 8 merge records per step, the threshold lists of 8 ranks concatenated,
     and the motif-sharded configs[2] leg (LPT over 2 346 motifs, 8 shares).  NOT a scaling number: one device."""
     out = run_bench("--gpus", "8", "--single-device", "--dist-backend", "gloo", "--steps", "2", "--warmup", "1",
-                    "--length", "50000000", "--preheat-ms", "20", "--cpu-seconds", "1", "--cpu-sample", "4000000", timeout=1500)
+                    "--length", "50000000", "--preheat-ms", "20", "--cpu-seconds", "1", "--cpu-sample", "4000000", "--full",
+                    timeout=1500)
     assert out["n_gpus"] == 8 and "invalid" not in out
     cfg = out["config"]
     assert cfg["parallelism"] == "row-shard x8" and cfg["halo_verified"] is True and cfg["process_group"] == "gloo x8"
     assert len(cfg["devices"]) == 8 and cfg["distinct_devices"] == 1
     whole = run_bench("--gpus", "1", "--steps", "2", "--warmup", "1", "--length", "400000000", "--preheat-ms", "20",
-                      "--no-cpu-baseline", "--no-extras")
+                      "--full", "--no-cpu-baseline", "--no-extras")
     assert out["extras"]["argmax_global"] == whole["extras"]["argmax_global"]     # 8 shards merge to the whole job's cell
     assert out["extras"]["threshold_hits"] > 0
     c3 = out["extras"]["configs"]["c3"]
@@ -107,7 +108,7 @@ def test_a_line_that_is_not_n_ranks_on_n_devices_fails_loudly():
 
 def test_single_gpu_line_has_every_contract_field():
     out = run_bench("--steps", "5", "--warmup", "2", "--length", "50000000", "--preheat-ms", "20", "--cpu-seconds", "2",
-                    "--cpu-sample", "16000000")
+                    "--cpu-sample", "16000000", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in out, key
@@ -159,3 +160,43 @@ def test_one_rank_through_the_c_abi_communicator():
     out = run_bench("--merge", "cabi", "--steps", "5", "--warmup", "2", "--length", "50000000", "--preheat-ms", "20",
                     "--no-cpu-baseline", "--no-extras")
     assert out["config"]["rccl_ranks"] == 1 and "C-ABI communicator" in out["config"]["merge_transport"]
+
+
+def test_plain_line_and_dumped_outputs(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the headline line without the legs that take runs of
+    their own; --dump-outputs writes the last step's score matrix (a seeded sample of its rows) bit-exact to the oracle."""
+    import importlib.util
+
+    import numpy as np
+    import torch
+    from oracle import c_oracle as co
+    length, m = 10_000_000, 20
+    out = run_bench("--steps", "3", "--warmup", "1", "--length", str(length), "--preheat-ms", "20",
+                    "--dump-outputs", str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["metric"] == "scored positions/sec" and out["unit"] == "Gpos/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["ms_per_step"] > 0
+    assert abs(out["value"] - length / (out["ms_per_step"] * 1e-3) / 1e9) < 0.02 * out["value"] + 0.05
+    assert out["cpu_baseline"] is None and "configs" not in out["extras"] and "argmax_ms" not in out["extras"]
+    files = sorted(p.name for p in tmp_path.iterdir())
+    assert files == ["score_positions.npy", "scores.npy"], files
+    assert sum(p.stat().st_size for p in tmp_path.iterdir()) <= 64 << 20
+    scores, positions = np.load(tmp_path / "scores.npy"), np.load(tmp_path / "score_positions.npy")
+    assert scores.dtype == np.float32 and positions.dtype == np.float64 and scores.shape == positions.shape
+    assert np.isfinite(scores).all()
+    rows = -(-length // 32)
+    pos = positions.astype(np.int64)
+    assert pos.min() == 0 and pos.max() == length - m and len(np.unique(pos)) == len(pos) < length - m + 1
+
+    spec = importlib.util.spec_from_file_location("lm_bench_dump", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    shard = bench.synth_shard(rows, 0, rows, length, 0, torch.device("cpu")).numpy()
+    enc = np.ascontiguousarray(shard.T).reshape(-1)[:length]     # position i sits at [i % rows][i / rows]
+    ref = co.stripe(enc, 32, 5)
+    co.configure_wrap(ref, m - 1)
+    want, _ = co.score_rows(ref, bench.synth_pssm(m).data)
+    assert want.shape[0] == rows
+    want = want[pos % rows, pos // rows]
+    assert np.array_equal(scores.view(np.uint32), want.view(np.uint32)), "dumped scores differ from the oracle"

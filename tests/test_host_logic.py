@@ -196,6 +196,48 @@ def test_bench_roofline_blocks_without_a_gpu():
     assert bench.best_kmer_score(pssm) == want
 
 
+def test_bench_dump_sample_without_a_gpu(tmp_path):
+    """--dump-outputs: the rows of the score matrix it writes are the same for the same arguments, ascending, disjoint,
+    within the budget, the first and the last rows included; the c3 hit lists are flattened in motif order, f32 / f64 only."""
+    import importlib.util
+    from pathlib import Path
+    spec = importlib.util.spec_from_file_location("lm_bench3", Path(__file__).resolve().parent.parent / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.dump_row_ranges(1000, 4096) == [(0, 1000)]
+    rows = 31_250_000
+    r = bench.dump_row_ranges(rows, bench.DUMP_ROWS)
+    assert r == bench.dump_row_ranges(rows, bench.DUMP_ROWS)
+    assert r[0] == (0, bench.DUMP_BLOCK) and r[-1] == (rows - bench.DUMP_BLOCK, rows)
+    assert sum(b - a for a, b in r) == bench.DUMP_ROWS and all(a < b for a, b in r)
+    assert all(r[i][1] <= r[i + 1][0] for i in range(len(r) - 1))
+    assert bench.DUMP_ROWS * 32 * (4 + 8) <= 64 << 20
+    # the scored positions of the sampled rows only (L - M + 1 of them): the cells past them read wrap / padding rows
+    rows, length, m = 5000, 5000 * 32 - 7, 20
+
+    class FakeScores:
+        def rows_matrix(self, a, b):
+            out = np.full((b - a, 40), -np.inf, np.float32)
+            out[:, :32] = np.arange(a * 32, b * 32, dtype=np.float32).reshape(-1, 32)
+            return out
+    bench.dump_scores(str(tmp_path / "c2"), FakeScores(), rows, 0, rows, length, m, 1, 0, False, None)
+    sc, pos = np.load(tmp_path / "c2" / "scores.npy"), np.load(tmp_path / "c2" / "score_positions.npy")
+    assert sc.dtype == np.float32 and pos.dtype == np.float64 and sc.shape == pos.shape
+    assert len(pos) == length - m + 1 and sorted(pos.tolist()) == list(range(length - m + 1))
+    row, col = pos.astype(np.int64) % rows, pos.astype(np.int64) // rows
+    assert np.array_equal(sc, (row * 32 + col).astype(np.float32))
+    assert bench.DUMP_HITS * (8 + 16 + 4) <= 64 << 20
+    res = [(np.array([[3, 1], [7, 30]], np.int64), np.array([1.5, 2.5], np.float32)),
+           (np.zeros((0, 2), np.int64), np.zeros(0, np.float32)),
+           (np.array([[0, 0]], np.int64), np.array([-1.0], np.float32))]
+    bench.dump_hits(str(tmp_path / "c3"), res)
+    got = {p.stem: np.load(p) for p in (tmp_path / "c3").iterdir()}
+    assert sorted(got) == ["hits_coords", "hits_motif", "hits_per_motif", "hits_scores"]
+    assert got["hits_per_motif"].tolist() == [2, 0, 1] and got["hits_motif"].tolist() == [0, 0, 2]
+    assert got["hits_coords"].tolist() == [[3, 1], [7, 30], [0, 0]] and got["hits_scores"].tolist() == [1.5, 2.5, -1.0]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+
+
 def test_no_built_artefact_is_tracked():
     """History stays source-only: nothing git tracks is an ELF object / executable / shared library (built `.so` files and
     the kbench tools travel to the GPU box untracked)."""

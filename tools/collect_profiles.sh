@@ -7,8 +7,8 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$ROOT"
-timeout 400 python bench.py > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
-timeout 300 python bench.py --config c3 > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
+timeout 400 python bench.py --full > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
+timeout 300 python bench.py --config c3 --full > "$OUT/bench_c3.json" 2> "$OUT/bench_c3.err"
 timeout 400 python tools/bench_configs.py > "$OUT/bench_configs.json" 2> "$OUT/bench_configs.err"
 timeout 200 python tools/api_overhead.py > "$OUT/api_overhead.json" 2> "$OUT/api_overhead.err"
 timeout 400 python tools/msweep.py > "$OUT/msweep.json" 2> "$OUT/msweep.err"
@@ -25,13 +25,13 @@ timeout 300 python tools/host_pointer_bench.py --json "$OUT/host_pointer.json" >
 # through a communicator of one rank -- functional checks, NOT scaling numbers
 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
     --master-port 29517 bench.py --gpus 2 --steps 20 --warmup 5 --dist-backend gloo --single-device \
-    --length 400000000 --no-cpu-baseline 2> "$OUT/bench_2rank.err" | grep '^{' > "$OUT/bench_2rank_gloo_single_device.json"
-timeout 200 python bench.py --merge cabi --steps 50 --warmup 10 --no-cpu-baseline > "$OUT/bench_cabi_merge_one_rank.json" 2> "$OUT/bench_cabi.err"
+    --length 400000000 --full --no-cpu-baseline 2> "$OUT/bench_2rank.err" | grep '^{' > "$OUT/bench_2rank_gloo_single_device.json"
+timeout 200 python bench.py --merge cabi --steps 50 --warmup 10 --full --no-cpu-baseline > "$OUT/bench_cabi_merge_one_rank.json" 2> "$OUT/bench_cabi.err"
 timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
     --master-port 29518 bench.py --config c3 --gpus 2 --steps 4 --warmup 1 --dist-backend gloo --single-device \
-    --no-cpu-baseline 2> "$OUT/bench_c3_2rank.err" | grep '^{' > "$OUT/bench_c3_2rank_gloo_single_device.json"
+    --full --no-cpu-baseline 2> "$OUT/bench_c3_2rank.err" | grep '^{' > "$OUT/bench_c3_2rank_gloo_single_device.json"
 ( cd /tmp && export TMPDIR=/tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv \
-    -d "$OUT/prof" -o bench -- python "$ROOT/bench.py" --no-cpu-baseline --no-extras > "$OUT/prof_bench.json" 2> "$OUT/prof.err" )
+    -d "$OUT/prof" -o bench -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extras > "$OUT/prof_bench.json" 2> "$OUT/prof.err" )
 # (--no-extras: the end-to-end extra launches the SAME store kernel on 262 144-row tiles through lm_hip_score_f32, which
 #  would be averaged into the headline kernel's row of the statistics)
 python - "$OUT" <<'PY'

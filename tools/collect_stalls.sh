@@ -1,12 +1,12 @@
 #!/bin/bash
 # Issue / stall breakdown of the library's kernels from the SQ counters (one counter group per
 # pass, --kernel-trace only: gpurun refuses --pmc together with the hip/hsa trace domains).
-#   gpurun --timeout 1200 -- 'bash tools/collect_stalls.sh r02 "python bench.py --steps 6 --warmup 3 --no-cpu-baseline --preheat-ms 0"'
+#   bash tools/collect_stalls.sh r02 "python bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --preheat-ms 0"
 # Units (MI355X_MICROARCH.md, "rocprofv3 PMC slots"): SQ_WAVE_CYCLES / SQ_WAIT_* / SQ_ACTIVE_INST_*
 # count quad-cycles summed over waves; WAIT_ANY + WAIT_INST_ANY + ACTIVE_INST_ANY ~ WAVE_CYCLES.
 TAG=${1:-r02}
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
-CMD=${2:-"python $ROOT/bench.py --steps 6 --warmup 3 --no-cpu-baseline --preheat-ms 0"}
+CMD=${2:-"python $ROOT/bench.py --full --steps 6 --warmup 3 --no-cpu-baseline --preheat-ms 0"}
 OUT=$ROOT/gpurun_out/stalls_$TAG
 rm -rf "$OUT"; mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp

@@ -1,5 +1,5 @@
-import sys, time, numpy as np
-sys.path.insert(0, "/root/repo")
+import os, sys, time, numpy as np
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 import lightmotif_amd as lm
 from lightmotif_amd import _ffi

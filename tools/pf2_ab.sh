@@ -3,11 +3,12 @@
 mkdir -p gpurun_out/pf2
 L=$PWD/lightmotif_amd/csrc
 O=gpurun_out/pf2/ab.txt
+ERR=${O%.txt}.err
 for rep in 1 2; do
   for tag in base "$@"; do
     if [ $tag = base ]; then unset LM_HIP_LIBRARY; else export LM_HIP_LIBRARY=$L/liblightmotif_hip_$tag.so; fi
     echo "== $tag rep$rep" >> $O
-    timeout 300 python bench.py --config c3 --steps 10 --warmup 3 --no-cpu-baseline 2>> gpurun_out/pf2/ab.err | python -c "
+    timeout 300 python bench.py --config c3 --steps 10 --warmup 3 --full --no-cpu-baseline 2>> "$ERR" | python -c "
 import sys, json
 for line in sys.stdin:
     if line.startswith('{'):

@@ -1,7 +1,7 @@
 """Every prefilter route (one symbol / pairs) against the exact fused kernel, protein and DNA, M = 4 ... 36, two p-values:
 prints MISMATCH lines (round 5 found the protein one-symbol kernels of M = 7, 8 this way).  python tools/prefilter_route_scan.py [length]"""
-import sys
-sys.path.insert(0,'/root/repo')
+import os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import lightmotif_amd as lm
 COLS=32

@@ -1,6 +1,6 @@
 import os, sys, time
 os.environ["LM_HIP_TRACE"]="1"
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tools')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__)))); sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import numpy as np, torch, bench
 import lightmotif_amd as lm
 torch.cuda.set_device(0); dev=torch.device("cuda",0)
