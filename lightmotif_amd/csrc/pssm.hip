@@ -4,6 +4,7 @@
 //   parts        slices of motifs beyond kMaxFastM rows
 //   d_image(2)   u16 images of the discrete prefilter scans (score_prefilter.hpp, score_prefilter2.hpp)
 #include <algorithm>
+#include <cfloat>
 #include <cmath>
 #include <new>
 
@@ -45,6 +46,11 @@ static bool build_prefilter(lm_hip_pssm &p, std::vector<unsigned> *image, std::v
         abs_sum += amax;
     }
     if (!(range > 0))
+        return false;
+    // A window's partial sums stay within abs_sum in real arithmetic and within abs_sum * (1 + (m - 1) * 2^-24 * 1.5)
+    // in f32; while that is below FLT_MAX none of them rounds to +-inf.  Above it a window can overflow to +inf (or
+    // to NaN, +inf + -inf) although its real sum lies below the threshold, which no image of real sums can flag.
+    if (abs_sum * (1.0 + (double)(m + 1) * std::ldexp(1.0, -23)) >= (double)FLT_MAX)
         return false;
     const double factor = range / (double)kPrefilterTop;
     // discrete weights d'[0..mp): leading zero rows pad the motif (even length; a multiple of 4 for wide alphabets)
@@ -90,7 +96,8 @@ static bool build_prefilter(lm_hip_pssm &p, std::vector<unsigned> *image, std::v
     }
     p.pre_offset = offset;
     p.pre_factor = factor;
-    // |f32 sum - real sum| <= (M-1) * 2^-24 * sum |terms|  (each add rounds to nearest)
+    // |f32 sum - real sum| <= (M-1) * 2^-24 * sum |terms|  (each add rounds to nearest; no partial sum overflows, see
+    // the abs_sum limit above -- a sum that rounds to +-inf has an unbounded error)
     p.pre_emax = (double)m * std::ldexp(1.0, -24) * abs_sum * 1.5;
     return true;
 }
