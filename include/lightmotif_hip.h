@@ -404,7 +404,12 @@ int lm_hip_configure_wrap_dptr(lm_hip_ctx *ctx, uint8_t *d_data, size_t rows, si
  * CLI), k = alphabet size (default symbol = k-1).  The `cols` live bytes of every row must
  * be symbols < k (LM_HIP_ERR_INVALID_SYMBOL otherwise; the reference's symbols are enums,
  * abc.rs:113-135).  The raw *_dptr entry points do NOT check this: bytes >= k there read
- * past the PSSM tables (garbage scores), which is the caller's precondition to keep. */
+ * past the PSSM tables (garbage scores), which is the caller's precondition to keep.
+ * Every entry point that takes a matrix (PSSM handle or discrete weights) AND a sequence
+ * handle returns LM_HIP_ERR_BAD_ARGS, before anything is launched, when the matrix's
+ * alphabet size differs from the handle's k (the reference's ScoringMatrix<A> and
+ * StripedSequence<A> share `A`).  The raw *_dptr and host-pointer forms carry no
+ * alphabet for the sequence: matching it there stays the caller's contract. */
 int lm_hip_seq_upload(lm_hip_ctx *ctx, const uint8_t *data, size_t rows_total, size_t stride,
                       size_t cols, size_t wrap, size_t length, size_t k, lm_hip_seq **out);
 /* The same for a matrix that already lives on the device and stays the CALLER's (a buffer of the

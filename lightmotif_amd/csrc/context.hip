@@ -74,6 +74,13 @@ int check_score_args(const lm_hip_pssm *pssm, size_t seq_rows_total, size_t seq_
     return LM_HIP_OK;
 }
 
+int check_alphabet(const char *what, size_t k, const lm_hip_seq *seq)
+{
+    if (seq && k != seq->k)
+        return fail(LM_HIP_ERR_BAD_ARGS, "%s: matrix alphabet of %zu symbols, sequence alphabet of %zu", what, k, seq->k);
+    return LM_HIP_OK;
+}
+
 // ---- result blocks ------------------------------------------------------------------------------
 // Host arrays handed to the caller (threshold / hit lists) and released with lm_hip_free.  A dense
 // hit list is tens of megabytes per call: a fresh malloc'ed block costs ~5 000 page faults while the

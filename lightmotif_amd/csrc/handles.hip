@@ -554,6 +554,7 @@ int lm_hip_score_rows_into(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_hi
     if (scores->cols != seq->cols)
         return fail(LM_HIP_ERR_BAD_ARGS, "score_rows_into: scores have %zu columns, sequence %zu",
                     scores->cols, seq->cols);
+    LM_TRY(check_alphabet("score_rows_into", pssm->k, seq));
     LM_TRY(check_score_args(pssm, seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap,
                             row_begin, row_end));
     std::lock_guard<std::mutex> lock(ctx->mu);

@@ -322,6 +322,9 @@ struct ScoreArgs {
 // Geometry checks shared by every score entry point (avx2.rs:832-837: the wrap check; row range inside the matrix)
 int check_score_args(const lm_hip_pssm *pssm, size_t seq_rows_total, size_t seq_stride, size_t cols, size_t wrap,
                      size_t row_begin, size_t row_end);
+// A matrix of alphabet size k against a sequence handle of another alphabet (the reference's shared `A` parameter of
+// ScoringMatrix<A> / StripedSequence<A>): LM_HIP_ERR_BAD_ARGS before anything runs -- symbols >= k read past the tables.
+int check_alphabet(const char *what, size_t k, const lm_hip_seq *seq);
 
 // Materialising score kernels.
 int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a);

@@ -85,6 +85,7 @@ int lm_hip_score_u8(lm_hip_ctx *ctx, const uint8_t *weights, size_t m, size_t we
     lm_hip_pssm shape;
     shape.m = m;
     shape.k = k;
+    LM_TRY(check_alphabet("score_u8", k, seq));
     LM_TRY(check_score_args(&shape, seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap, row_begin,
                             row_end));
     if (seq->length < m || row_begin >= row_end) {  // pli/mod.rs:85-88
@@ -289,6 +290,8 @@ static int batch_jobs(const lm_hip_pssm *const *pssms, size_t n, const lm_hip_se
     jobs->clear();
     degenerate->assign(n, 0);
     for (size_t i = 0; i < n; ++i) {
+        if (pssms[i])
+            LM_TRY(check_alphabet("scan batch", pssms[i]->k, seq));
         LM_TRY(check_score_args(pssms[i], seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap,
                                 0, seq->rows));
         if (seq->length < pssms[i]->m || seq->rows == 0)
@@ -381,6 +384,7 @@ int lm_hip_scan_f32(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_hip_seq *
         return fail(LM_HIP_ERR_BAD_ARGS, "scan: null argument");
     *hits = nullptr;
     *n = 0;
+    LM_TRY(check_alphabet("scan", pssm->k, seq));
     LM_TRY(check_score_args(pssm, seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap, 0,
                             seq->rows));
     if (seq->length < pssm->m || seq->rows == 0)
@@ -418,6 +422,7 @@ int lm_hip_scan_max_f32(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_hip_s
         return fail(LM_HIP_ERR_BAD_ARGS, "scan_max: null argument");
     if (dweights_stride < pssm->k)
         return fail(LM_HIP_ERR_BAD_ARGS, "scan_max: discrete weights stride %zu < alphabet size %zu", dweights_stride, pssm->k);
+    LM_TRY(check_alphabet("scan_max", pssm->k, seq));
     LM_TRY(check_score_args(pssm, seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap, 0, seq->rows));
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard guard(ctx->device);

@@ -44,6 +44,14 @@ def _k(protein: bool) -> int:
     return len(_symbols(protein))
 
 
+def _same_alphabet(matrix, seq: "StripedSequence") -> None:
+    """The reference's ``ScoringMatrix<A>`` / ``StripedSequence<A>`` share the alphabet parameter; here a mismatch is a
+    ``ValueError`` before anything runs (the fused forms hand the C ABI a raw data pointer, which it cannot check)."""
+    if matrix.protein != seq.protein:
+        raise ValueError(f"{'protein' if matrix.protein else 'DNA'} matrix against a "
+                         f"{'protein' if seq.protein else 'DNA'} sequence")
+
+
 def stride(cols: int, elem_size: int) -> int:
     """DenseMatrix::stride (dense.rs:126-128)."""
     return int(_ffi.lib().lm_hip_stride(cols, elem_size))
@@ -285,11 +293,13 @@ class Pipeline:
 
     def score_rows_into(self, pssm: "ScoringMatrix", seq: "StripedSequence", rows: range,
                         scores: "StripedScores") -> None:
+        _same_alphabet(pssm, seq)
         check(self._L.lm_hip_score_rows_into(self._h, pssm._device(self), seq._h,
                                              rows.start, max(rows.stop, rows.start), scores._h))
 
     def score_into(self, pssm: "ScoringMatrix", seq: "StripedSequence",
                    scores: "StripedScores") -> None:
+        _same_alphabet(pssm, seq)
         check(self._L.lm_hip_score_into(self._h, pssm._device(self), seq._h, scores._h))
 
     def score(self, pssm: "ScoringMatrix", seq: "StripedSequence") -> "StripedScores":
@@ -341,6 +351,7 @@ class Pipeline:
     def score_argmax(self, pssm: "ScoringMatrix", seq: "StripedSequence",
                      rows: Optional[range] = None):
         """score_rows_into + argmax without writing the scores: ((row, col), value) or None."""
+        _same_alphabet(pssm, seq)
         length, wrap, nrows, stride_, columns, data_ptr = seq._info()    # one call: a small scan is latency-bound
         rows = range(0, nrows) if rows is None else rows
         found, best, value = C.c_int(0), Coords(), C.c_float(0)
@@ -353,6 +364,7 @@ class Pipeline:
     def score_threshold(self, pssm: "ScoringMatrix", seq: "StripedSequence", threshold: float,
                         rows: Optional[range] = None):
         """score_rows_into + threshold without writing the scores: ([(row, col)], [value])."""
+        _same_alphabet(pssm, seq)
         length, wrap, nrows, stride_, columns, data_ptr = seq._info()
         rows = range(0, nrows) if rows is None else rows
         ptr, vals, n = C.POINTER(Coords)(), C.POINTER(C.c_float)(), C.c_size_t(0)
@@ -371,6 +383,8 @@ class Pipeline:
 
     def scan_argmax_batch(self, pssms: Sequence["ScoringMatrix"], seq: "StripedSequence"):
         """Per motif: ``((row, col), value)`` of the best cell, or ``None`` (L < M)."""
+        if any(p.protein != seq.protein for p in pssms):
+            _same_alphabet(next(p for p in pssms if p.protein != seq.protein), seq)
         n = len(pssms)
         handles = (C.c_void_p * n)(*[p._device(self) for p in pssms])
         found = (C.c_int * n)()
@@ -389,6 +403,8 @@ class Pipeline:
         """Per motif: ``(coords (n_i, 2) int64 in row-major order, values (n_i,) f32)`` -- a sequence of such pairs (views
         into ONE pair of arrays the library returned, cut on access)."""
         batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms, thresholds)
+        if batch.protein - {seq.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seq.protein), seq)
         n = len(batch)
         counts = np.zeros(n, dtype=np.uintp)
         ptr, vals = C.POINTER(Coords)(), C.POINTER(C.c_float)()
@@ -449,6 +465,7 @@ class Pipeline:
         """``Score<u8, ..>::score_rows_into(&dm, &seq, rows, &mut scores)`` (pli/mod.rs:72-106):
         the u8 score matrix ``(rows, stride(C, 1))`` on the host and ``max_index``.
         ``saturate``: the SIMD back-ends' saturating adds (avx2.rs:336) or Generic's wrapping."""
+        _same_alphabet(dm, seq)
         rows = range(0, seq.rows) if rows is None else rows
         n = max(rows.stop - rows.start, 0)
         st = stride(seq.columns, 1)
@@ -965,6 +982,7 @@ class MotifBatch:
 
     def __init__(self, pli: "Pipeline", pssms: Sequence["ScoringMatrix"], thresholds: Optional[Sequence[float]] = None):
         self.pssms = list(pssms)          # (keeps the matrices, hence their device tables, alive)
+        self.protein = {p.protein for p in self.pssms}  # the alphabets present (checked against each sequence)
         n = len(self.pssms)
         self.handles = (C.c_void_p * n)(*[p._device(pli) for p in self.pssms])
         self.thresholds = None
