@@ -76,9 +76,18 @@ typedef struct lm_hip_hit {
     float score;
 } lm_hip_hit;
 
+/* One hit of a scan over a sequence set: the record and the position INSIDE that record (main.rs:527-531 writes
+ * exactly this pair per line of the CLI's table). */
+typedef struct lm_hip_set_hit {
+    size_t record;
+    size_t position;
+    float score;
+} lm_hip_set_hit;
+
 typedef struct lm_hip_ctx lm_hip_ctx;       /* device + stream + scratch */
 typedef struct lm_hip_pssm lm_hip_pssm;     /* ScoringMatrix data resident on the device */
 typedef struct lm_hip_seq lm_hip_seq;       /* StripedSequence resident on the device */
+typedef struct lm_hip_seqset lm_hip_seqset; /* many records resident as one StripedSequence + their offsets */
 typedef struct lm_hip_scores lm_hip_scores; /* StripedScores<f32> resident on the device */
 typedef struct lm_hip_comm lm_hip_comm;     /* RCCL communicator of a row-sharded job */
 
@@ -340,6 +349,51 @@ int lm_hip_scan_argmax_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, s
 int lm_hip_scan_threshold_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms,
                                 const float *thresholds, size_t n, const lm_hip_seq *seq,
                                 size_t *counts, lm_hip_coords **coords, float **values);
+
+/* ---- many motifs x many resident sequences --------------------------------- */
+
+/* The other axis of the CLI's job product (main.rs:502-561: one job per (motif, record) pair): a SET of records --
+ * a peak set, promoters, contigs -- resident as ONE striped sequence, so that the per-call costs (upload, stripe,
+ * synchronisation, read-back) are paid once per set instead of once per record.  The records are laid end to end
+ * WITHOUT separators: the matrix is exactly StripedSequence of the joined text (seq.rs:288-313), and since a score is
+ * M sequential f32 adds over symbols p .. p+M-1 (pli/mod.rs:72-106) every window inside one record scores bit for
+ * bit as it does when the record is striped alone.
+ *   text / encoded   `total` bytes: ASCII (alphabet 'D' / 'P', strict or lossy as lm_hip_seq_from_ascii) or symbol
+ *                    bytes < k (as lm_hip_seq_from_encoded); one upload, encode + stripe on the device
+ *   offsets          n_records + 1 entries: record r is [offsets[r], offsets[r+1]); offsets[0] == 0, non-decreasing
+ *                    (empty records are fine), offsets[n_records] == total -- LM_HIP_ERR_BAD_ARGS otherwise, checked
+ *                    before any device work.  The table is kept on the device next to the matrix, 64-bit entries.
+ *   bad_record / bad_index   strict mode: the first invalid byte as (record, index inside the record) with
+ *                    LM_HIP_ERR_INVALID_SYMBOL; either may be NULL
+ * LM_HIP_ERR_CAPACITY when ceil(total / cols) * cols exceeds the 2^40 cells a hit list addresses, LM_HIP_ERR_OOM when
+ * the device cannot hold the matrix. */
+int lm_hip_seqset_from_ascii(lm_hip_ctx *ctx, char alphabet, const uint8_t *text, size_t total,
+                             const uint64_t *offsets, size_t n_records, size_t cols, int lossy,
+                             lm_hip_seqset **out, size_t *bad_record, size_t *bad_index);
+int lm_hip_seqset_from_encoded(lm_hip_ctx *ctx, const uint8_t *encoded, size_t total,
+                               const uint64_t *offsets, size_t n_records, size_t cols, size_t k,
+                               lm_hip_seqset **out);
+/* StripedSequence::configure_wrap (seq.rs:369-381) on the set's matrix (the CLI: configure_wrap(max_m), main.rs:540-546). */
+int lm_hip_seqset_configure_wrap(lm_hip_ctx *ctx, lm_hip_seqset *set, size_t m);
+/* records, len() of the concatenation, matrix().rows() - wrap(), wrap(), cols, alphabet size; any pointer may be NULL. */
+int lm_hip_seqset_info(const lm_hip_seqset *set, size_t *records, size_t *total_length, size_t *rows,
+                       size_t *wrap, size_t *cols, size_t *k);
+int lm_hip_seqset_record_length(const lm_hip_seqset *set, size_t record, size_t *length);
+/* All record lengths at once; LM_HIP_ERR_CAPACITY when `capacity` < records. */
+int lm_hip_seqset_lengths(const lm_hip_seqset *set, size_t *lengths, size_t capacity);
+int lm_hip_seqset_destroy(lm_hip_seqset *set);
+
+/* `n` motifs x every record of the set in ONE call (main.rs:502-561 collapsed): per motif, in caller order, every
+ * (record, position) with score >= threshold and position + M <= len(record) (scan.rs:185-190, per RECORD), sorted by
+ * record, then position.  counts[i] hits for motif i; *hits holds sum(counts) entries (release with lm_hip_free; NULL
+ * when there are none).  Scores and hit sets equal, bit for bit, lm_hip_scan_threshold_batch + that cut on each record
+ * striped alone; NaN / -inf thresholds and weights behave as there.  The scans are those of
+ * lm_hip_scan_threshold_batch over the concatenation; windows that straddle two records or run past a record's end
+ * are dropped, and positions made record-relative, by a segment pass on the device (csrc/seqset.hip) before anything
+ * is read back.  LM_HIP_ERR_WRAP when the set's wrap < max(M) - 1; LM_HIP_ERR_BAD_ARGS, before any launch, when a
+ * matrix's alphabet size differs from the set's.  A motif longer than every record has no hits. */
+int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds,
+                                 size_t n, const lm_hip_seqset *set, size_t *counts, lm_hip_set_hit **hits);
 
 /* Scanner (scan.rs:96-250), collected: every position with score >= threshold and
  * position + M <= L (scan.rs:185-190), as (position, f32 score) sorted by position

@@ -23,6 +23,10 @@ class Hit(C.Structure):
     _fields_ = [("position", C.c_size_t), ("score", C.c_float)]
 
 
+class SetHit(C.Structure):
+    _fields_ = [("record", C.c_size_t), ("position", C.c_size_t), ("score", C.c_float)]
+
+
 class LightmotifHipError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"lightmotif_hip error {status}: {message}")
@@ -95,6 +99,14 @@ SIGNATURES = {
     "lm_hip_scan_argmax_batch": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _ip, _cp, _fp]),
     "lm_hip_scan_threshold_batch": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _szp,
                                               C.POINTER(_cp), C.POINTER(_fp)]),
+    "lm_hip_seqset_from_ascii": (C.c_int, [_vp, C.c_char, _vp, _sz, _vp, _sz, _sz, C.c_int, C.POINTER(_vp), _szp, _szp]),
+    "lm_hip_seqset_from_encoded": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.POINTER(_vp)]),
+    "lm_hip_seqset_configure_wrap": (C.c_int, [_vp, _vp, _sz]),
+    "lm_hip_seqset_info": (C.c_int, [_vp, _szp, _szp, _szp, _szp, _szp, _szp]),
+    "lm_hip_seqset_record_length": (C.c_int, [_vp, _sz, _szp]),
+    "lm_hip_seqset_lengths": (C.c_int, [_vp, _vp, _sz]),
+    "lm_hip_seqset_destroy": (C.c_int, [_vp]),
+    "lm_hip_scan_threshold_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _szp, C.POINTER(C.POINTER(SetHit))]),
     "lm_hip_scan_f32": (C.c_int, [_vp, _vp, _vp, C.c_float, C.POINTER(C.POINTER(Hit)), _szp]),
     "lm_hip_scan_max_f32": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_int, C.c_uint, C.c_int, _sz, C.c_float, _sz, _ip,
                                       C.POINTER(Hit)]),

@@ -97,6 +97,7 @@ __global__ __launch_bounds__(kBlock) void hits_bucket_scatter(
 
 // EMIT 0: lm_hip_coords {low / cols, low % cols} + score (Threshold, pli/mod.rs:215)
 // EMIT 1: lm_hip_hit {low, score} (Scanner: low is the sequence position)
+// EMIT 2: the record itself, key included, into `out_hits` (a device list for the segment pass of seqset.hip)
 template <int EMIT>
 __global__ __launch_bounds__(kBlock) void hits_rank_emit(
     const HitRecord *__restrict__ grouped, const unsigned long long *__restrict__ count_ptr,
@@ -158,13 +159,15 @@ __global__ __launch_bounds__(kBlock) void hits_rank_emit(
                 static_cast<lm_hip_coords *>(pre_out)[pos] = c;
                 pre_values[pos] = r.value;
             }
-        } else {
+        } else if (EMIT == 1) {
             lm_hip_hit h;
             h.position = low;
             h.score = r.value;
             out_hits[pos] = h;
             if (pos < pre)
                 static_cast<lm_hip_hit *>(pre_out)[pos] = h;
+        } else {
+            reinterpret_cast<HitRecord *>(out_hits)[pos] = r;
         }
     }
     // ShortOrder: the host polls a word in the pinned staging block instead of waiting for the kernel's completion signal
@@ -356,13 +359,19 @@ __global__ __launch_bounds__(kBlock) void hits_sorted_emit(
                 static_cast<lm_hip_coords *>(pre_out)[pos] = c;
                 pre_values[pos] = v;
             }
-        } else {
+        } else if (EMIT == 1) {
             lm_hip_hit h;
             h.position = low;
             h.score = v;
             out_hits[pos] = h;
             if (pos < pre)
                 static_cast<lm_hip_hit *>(pre_out)[pos] = h;
+        } else {
+            HitRecord r;
+            r.key = keys[pos];
+            r.value = v;
+            r.pad = 0;
+            reinterpret_cast<HitRecord *>(out_hits)[pos] = r;
         }
     }
 }
@@ -422,6 +431,8 @@ void HitOutput::release()
     result_free(coords);
     result_free(values);
     result_free(hits);
+    result_free(set_hits);
+    set_hits = nullptr;
     coords = nullptr;
     values = nullptr;
     hits = nullptr;
@@ -445,8 +456,11 @@ constexpr unsigned long long kPrefix = 12800;  // x 20 B = 256 KB
 int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long long *d_counters,
                unsigned long long count, unsigned long long cap, unsigned long long cand_cap,
                unsigned long long expected, size_t njobs, unsigned long long max_low, int emit, size_t cols,
-               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so)
+               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so, const SegmentCut *cut)
 {
+    static_assert(sizeof(HitRecord) == sizeof(lm_hip_hit), "EMIT 2 writes records where EMIT 1 writes lm_hip_hit");
+    if (cut && (emit != 1 || (so && so->on)))
+        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the segment pass needs position keys and the long ordering");
     const bool speculative = count == ~0ull;
     *status = 0;
     out->job_start.assign(njobs + 1, 0);
@@ -495,17 +509,24 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     // bounded so that the staging copy stays a small pinned transfer
     const unsigned long long pre =
         speculative ? std::min(room, std::min<unsigned long long>(std::max<unsigned long long>(sized_for, 2048), kPrefix)) : 0;
+    const unsigned long long order_pre = cut ? 0 : pre;  // (with a segment pass the head of ITS output is mirrored)
     // exact form: starts | records | values contiguous in scratch2 (one read-back copy)
     const size_t off_starts = off_total + 16;
     const size_t off_out = off_starts + align16((njobs + 1) * 8);
     const size_t off_values = off_out + align16(room * rec_bytes);
-    const size_t bytes = off_values + align16(room * sizeof(float));
+    // segment pass (seqset.hip): survivors per wavefront | the jobs' new starts | the compacted (record, position, score) list
+    const unsigned seg_grid = (unsigned)std::max<unsigned long long>(
+        std::min<unsigned long long>((sized_for + 1023) / 1024, (unsigned long long)ctx->num_cus * 4), 1);
+    const size_t off_seg_counts = off_values + align16(room * sizeof(float));
+    const size_t off_seg_starts = off_seg_counts + (cut ? align16(segment_cut_waves(seg_grid) * 4) : 0);
+    const size_t off_seg_out = off_seg_starts + (cut ? align16((njobs + 1) * 8) : 0);
+    const size_t bytes = off_seg_out + (cut ? align16(room * sizeof(lm_hip_set_hit)) : 0);
     // speculative form: the staging block -- counters | abort flag | starts | head of the list --
     // lives in the context's pinned host buffer and the kernels write it THERE (posted writes
     // over PCIe, visible after the stream synchronisation): no copy command, no memset
     const size_t p_abort = 16, p_starts = 32;
     const size_t p_out = p_starts + align16((njobs + 1) * 8);
-    const size_t p_values = p_out + align16(pre * rec_bytes);
+    const size_t p_values = p_out + align16(pre * (cut ? sizeof(lm_hip_set_hit) : rec_bytes));
     const size_t p_bytes = p_values + align16(pre * sizeof(float));
     char *pin = static_cast<char *>(ctx->pinned);
     static_assert(sizeof(size_t) == 8, "job offsets are read back as 64-bit values");
@@ -538,7 +559,10 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     void *pre_out = pin + p_out;
     float *pre_values = reinterpret_cast<float *>(pin + p_values);
     unsigned long long *starts =
-        reinterpret_cast<unsigned long long *>(speculative ? pin + p_starts : base + off_starts);
+        reinterpret_cast<unsigned long long *>(speculative && !cut ? pin + p_starts : base + off_starts);
+    // with a segment pass the ordering's own starts stay on the device (unused); the starts of the compacted list take their place
+    unsigned long long *seg_starts = reinterpret_cast<unsigned long long *>(speculative ? pin + p_starts : base + off_seg_starts);
+    lm_hip_set_hit *d_set = reinterpret_cast<lm_hip_set_hit *>(base + off_seg_out);
     void *d_out = base + off_out;
     float *d_values = reinterpret_cast<float *>(base + off_values);
     if (speculative)
@@ -578,6 +602,11 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
                                (unsigned long long)cols, static_cast<lm_hip_coords *>(d_out), d_values,
                                static_cast<lm_hip_hit *>(nullptr), pre_out, pre_values, pre,
                                speculative ? header : static_cast<unsigned long long *>(nullptr));
+        else if (cut)
+            hipLaunchKernelGGL(hits_sorted_emit<2>, dim3(grid), dim3(kBlock), 0, st, keys_out, vals_out, d_counters, cap, n_sort,
+                               (unsigned long long)cols, static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
+                               static_cast<lm_hip_hit *>(d_out), pre_out, pre_values, order_pre,
+                               speculative ? header : static_cast<unsigned long long *>(nullptr));
         else
             hipLaunchKernelGGL(hits_sorted_emit<1>, dim3(grid), dim3(kBlock), 0, st, keys_out, vals_out, d_counters, cap, n_sort,
                                (unsigned long long)cols, static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
@@ -609,6 +638,14 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
                            (unsigned long long)njobs, inline_starts ? starts : nullptr, inline_starts && speculative ? header : nullptr,
                            short_form ? counts : nullptr, cursors, short_form ? so->counters : nullptr, done_ticket, done_flag,
                            generation);
+    else if (cut)
+        hipLaunchKernelGGL(hits_rank_emit<2>, dim3(grid), dim3(kBlock), 0, st, grouped, rank_counters, cap, shift,
+                           nb, nbuckets, offsets, tiles, (unsigned long long)cols,
+                           static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
+                           static_cast<lm_hip_hit *>(d_out), max_bucket, abort_flag, pre_out, pre_values, order_pre,
+                           (unsigned long long)njobs, inline_starts ? starts : nullptr, inline_starts && speculative ? header : nullptr,
+                           static_cast<unsigned *>(nullptr), cursors, static_cast<unsigned long long *>(nullptr), done_ticket, done_flag,
+                           generation);
     else
         hipLaunchKernelGGL(hits_rank_emit<1>, dim3(grid), dim3(kBlock), 0, st, grouped, rank_counters, cap, shift,
                            nb, nbuckets, offsets, tiles, (unsigned long long)cols,
@@ -624,7 +661,55 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     LM_HIP_TRY(hipGetLastError());
     }
 
+    if (cut)  // drop the windows that leave their record, make the others record-relative, per-job starts anew (seqset.hip)
+        LM_TRY(launch_segment_cut(st, static_cast<const HitRecord *>(d_out), d_counters, sorted ? n_sort : room, njobs, *cut, seg_grid,
+                                  reinterpret_cast<unsigned *>(base + off_seg_counts), seg_starts, d_set,
+                                  static_cast<lm_hip_set_hit *>(pre_out), pre));
     scan_timer_mark(ctx, st, 3);  // (time_scan) behind the ordering kernels
+    if (cut) {
+        // the read-back of the compacted list: as below, with the survivors' count = the last of the new starts
+        if (speculative) {
+            LM_HIP_TRY(hipStreamSynchronize(st));
+            counts_out[0] = reinterpret_cast<unsigned long long *>(pin)[0];
+            counts_out[1] = reinterpret_cast<unsigned long long *>(pin)[1];
+            if (counts_out[0] > cap || counts_out[1] > cand_cap) {
+                *status = 1;
+                return LM_HIP_OK;
+            }
+            if (*reinterpret_cast<unsigned *>(pin + p_abort)) {
+                *status = 2;
+                return LM_HIP_OK;
+            }
+            if (counts_out[0] == 0)
+                return LM_HIP_OK;
+            memcpy(out->job_start.data(), pin + p_starts, starts_bytes);
+        } else {
+            LM_HIP_TRY(hipMemcpyAsync(out->job_start.data(), seg_starts, starts_bytes, hipMemcpyDeviceToHost, st));
+            LM_HIP_TRY(hipStreamSynchronize(st));
+        }
+        const unsigned long long kept = out->job_start[njobs];
+        if (kept > room)
+            return fail(LM_HIP_ERR_HIP, "fused threshold: the segment pass reports %llu of %llu hits", kept, room);
+        if (kept == 0)
+            return LM_HIP_OK;
+        lm_hip_set_hit *host = static_cast<lm_hip_set_hit *>(result_alloc(kept * sizeof(lm_hip_set_hit)));
+        if (!host)
+            return fail(LM_HIP_ERR_OOM, "fused threshold: cannot allocate %llu hits on the host", kept);
+        const unsigned long long have = speculative ? std::min(kept, pre) : 0;
+        memcpy(host, pin + p_out, have * sizeof(lm_hip_set_hit));
+        if (kept > have) {  // long list: the rest comes straight from the device
+            hipError_t e = hipMemcpyAsync(host + have, d_set + have, (kept - have) * sizeof(lm_hip_set_hit), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(st);
+            if (e != hipSuccess) {
+                result_free(host);
+                return fail(LM_HIP_ERR_HIP, "fused threshold: read-back failed: %s", hipGetErrorString(e));
+            }
+        }
+        out->total = (size_t)kept;
+        out->set_hits = host;
+        return LM_HIP_OK;
+    }
     if (speculative) {
         bool seen = false;
         if (done_flag) {  // the ranking kernel's last workgroup raises the word behind everything it and the others wrote

@@ -238,6 +238,15 @@ struct lm_hip_seq {
     bool owns = true;          // false: d_data is the caller's (lm_hip_seq_adopt_dptr)
 };
 
+// Many records resident as ONE striped sequence (seqset.hip): `seq` is StripedSequence of the joined text, record r is
+// symbols [offsets[r], offsets[r + 1]) of it; the table lives on the device as well (64-bit entries).
+struct lm_hip_seqset {
+    int device = 0;
+    lm_hip_seq *seq = nullptr;
+    std::vector<uint64_t> offsets;           // n_records + 1
+    unsigned long long *d_offsets = nullptr;
+};
+
 struct lm_hip_scores {
     int device = 0;
     float *d_data = nullptr;
@@ -377,6 +386,7 @@ struct HitOutput {
     lm_hip_coords *coords = nullptr;  // HitKeys::RowMajor: (row, col) + values
     float *values = nullptr;
     lm_hip_hit *hits = nullptr;       // HitKeys::Position: (sequence position, score)
+    lm_hip_set_hit *set_hits = nullptr;  // ... with a SegmentCut: (record, position in the record, score)
     void release();
 };
 
@@ -385,10 +395,21 @@ struct HitOutput {
 // (scores.rs:155-157) for Scanner-style output.
 enum class HitKeys { RowMajor, Position };
 
+// The jobs scan a concatenation of records (lm_hip_seqset): behind the ordering, on the device, hits whose window does
+// not lie inside one record are dropped and the others become (record, position in the record) -- seqset.hip.
+struct SegmentCut {
+    const unsigned long long *d_offsets = nullptr;  // n_records + 1 entries, device
+    unsigned long long n_records = 0;
+    // motif length of job j: the u32 at d_job_m + j * job_m_stride (device; filled in by launch_score_threshold_batch)
+    const void *d_job_m = nullptr;
+    size_t job_m_stride = 0;
+};
+
 // Fused score+threshold of n independent jobs (row indices relative to each job's
-// row_begin).  HitKeys::Position requires row_begin == 0 on every job.
+// row_begin).  HitKeys::Position requires row_begin == 0 on every job; `cut` (Position keys only) turns the result
+// into out->set_hits.
 int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const float *ts, size_t n,
-                                 HitKeys keys, HitOutput *out);
+                                 HitKeys keys, HitOutput *out, const SegmentCut *cut = nullptr);
 
 // Batched fused score+argmax: n independent jobs, one stream synchronisation.
 int launch_score_argmax_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
@@ -413,7 +434,14 @@ int short_order_begin(lm_hip_ctx *ctx, unsigned long long expected, size_t njobs
 int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long long *d_counters,
                unsigned long long count, unsigned long long cap, unsigned long long cand_cap,
                unsigned long long expected, size_t njobs, unsigned long long max_low, int emit, size_t cols,
-               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so = nullptr);
+               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so = nullptr,
+               const SegmentCut *cut = nullptr);
+// seqset.hip: the two launches of the segment pass over `ordered` (records with their full keys, in key order; the
+// count is read from the device).  `grid` workgroups; wave_counts needs segment_cut_waves(grid) entries.
+unsigned segment_cut_waves(unsigned grid);
+int launch_segment_cut(hipStream_t st, const HitRecord *ordered, const unsigned long long *count_ptr, unsigned long long room,
+                       unsigned long long njobs, const SegmentCut &seg, unsigned grid, unsigned *wave_counts,
+                       unsigned long long *starts, lm_hip_set_hit *out, lm_hip_set_hit *pre_out, unsigned long long pre);
 
 // reduce.hip: exclusive scan of n u32 counts (async on ctx->stream); the offset of
 // element i is tiles[i / kScanTile] + offsets[i], *total the grand total.

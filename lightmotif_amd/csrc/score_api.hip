@@ -377,6 +377,49 @@ int lm_hip_scan_threshold_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms
     return LM_HIP_OK;
 }
 
+// ---- many motifs x many resident sequences (main.rs:502-561) -----------------------------------------------
+
+// The scans of lm_hip_scan_threshold_batch over the concatenation, keyed by sequence position; the segment pass of
+// seqset.hip then cuts at `position + M <= len(record)` (scan.rs:185-190) on the device.
+int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds, size_t n,
+                                 const lm_hip_seqset *set, size_t *counts, lm_hip_set_hit **hits)
+{
+    if (!ctx || !set || !hits || (n && (!counts || !thresholds)))
+        return fail(LM_HIP_ERR_BAD_ARGS, "scan_threshold_seqset: null argument");
+    *hits = nullptr;
+    const lm_hip_seq *seq = set->seq;
+    std::vector<ScoreArgs> jobs;
+    std::vector<char> degenerate;
+    LM_TRY(batch_jobs(pssms, n, seq, &jobs, &degenerate));
+    std::vector<ScoreArgs> live;
+    std::vector<float> live_t;
+    std::vector<size_t> live_idx;
+    for (size_t i = 0; i < n; ++i) {
+        counts[i] = 0;
+        if (!degenerate[i]) {
+            live.push_back(jobs[i]);
+            live_t.push_back(thresholds[i]);
+            live_idx.push_back(i);
+        }
+    }
+    if (live.empty())
+        return LM_HIP_OK;
+    SegmentCut cut;
+    cut.d_offsets = set->d_offsets;
+    cut.n_records = set->offsets.size() - 1;
+    HitOutput ho;
+    {
+        std::lock_guard<std::mutex> lock(ctx->mu);
+        DeviceGuard guard(ctx->device);
+        ScratchTrim trim(ctx);
+        LM_TRY(launch_score_threshold_batch(ctx, live.data(), live_t.data(), live.size(), HitKeys::Position, &ho, &cut));
+    }
+    for (size_t k = 0; k < live.size(); ++k)
+        counts[live_idx[k]] = ho.job_start[k + 1] - ho.job_start[k];
+    *hits = ho.set_hits;
+    return LM_HIP_OK;
+}
+
 int lm_hip_scan_f32(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_hip_seq *seq,
                     float threshold, lm_hip_hit **hits, size_t *n)
 {

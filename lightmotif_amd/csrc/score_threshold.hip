@@ -217,8 +217,10 @@ int launch_rescore(lm_hip_ctx *ctx, hipStream_t st, const RescoreJob *d_jobs, co
 // enqueued behind the scans (hits.hip: speculative form), two when the count is read first.
 // Equal-length DNA motifs of a batch share passes over the sequence (score_c32_prefilter2_multi).
 int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const float *ts, size_t n,
-                                 HitKeys keys, HitOutput *out)
+                                 HitKeys keys, HitOutput *out, const SegmentCut *cut)
 {
+    if (cut && keys != HitKeys::Position)
+        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the segment pass needs position keys");
     out->job_start.assign(n + 1, 0);
     out->total = 0;
     if (n == 0)
@@ -354,7 +356,8 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         // bucket as well, and the counters live in the context -- nothing to copy in before the scan (hits.hip, ShortOrder)
         ShortOrder so;
         const unsigned long long expected = ctx->last_hit_count + ctx->last_hit_count / 4;
-        if (attempt == 0 && ctx->speculate_order && ctx->short_order && n == 1 && groups.size() == 1 &&
+        // (not for a sequence set: the segment pass reads the job table and sits behind the long ordering)
+        if (attempt == 0 && !cut && ctx->speculate_order && ctx->short_order && n == 1 && groups.size() == 1 &&
             (groups[0].kind == KIND_PREFILTER || groups[0].kind == KIND_PREFILTER2 || groups[0].kind == KIND_EXACT))
             LM_TRY(short_order_begin(ctx, expected, n, max_low, &so));
         if (so.on) {
@@ -448,6 +451,13 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         }
         scan_timer_mark(ctx, ctx->stream, 2);
         const int emit = keys == HitKeys::Position ? 1 : 0;
+        SegmentCut seg;
+        if (cut) {  // motif lengths come from the job table the re-scoring kernel reads (it moves with the scratch block)
+            seg = *cut;
+            seg.d_job_m = reinterpret_cast<const char *>(d_jobs) + offsetof(RescoreJob, m);
+            seg.job_m_stride = sizeof(RescoreJob);
+        }
+        const SegmentCut *segp = cut ? &seg : nullptr;
         unsigned long long count = 0, ncand = 0;
         const auto t_scan = std::chrono::steady_clock::now();
         bool ordered = false;
@@ -457,7 +467,7 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
             int status = 0;
             unsigned long long counts[2] = {0, 0};
             LM_TRY(order_hits(ctx, fo.hits, fo.hit_count, ~0ull, cap, ccap, expected, n, max_low, emit, jobs[0].cols, out,
-                              &status, counts, &so));
+                              &status, counts, &so, segp));
             count = counts[0];
             ncand = counts[1];
             ordered = status == 0;
@@ -495,7 +505,7 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
             unsigned long long counts[2];
             // (after a short form that gave up, the list's counters have been cleared: their copy still holds them)
             LM_TRY(order_hits(ctx, fo.hits, so.on ? so.counters_copy : fo.hit_count, count, cap, ccap, count, n, max_low, emit, jobs[0].cols,
-                              out, &status, counts));
+                              out, &status, counts, nullptr, segp));
         }
         scan_timer_read(ctx);
         if (ctx->last_phase_ms[0] >= 0)  // (time_scan) the host's share: everything of the call the events do not cover

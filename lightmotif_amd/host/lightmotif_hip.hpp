@@ -186,6 +186,50 @@ private:
     lm_hip_seq *h_;
 };
 
+// Many records resident as ONE striped sequence (lm_hip_seqset): the records' texts joined without separators plus
+// the table of record offsets on the device -- the sequence axis of the CLI's job product (main.rs:502-561).
+template <class A>
+class SequenceSet {
+public:
+    SequenceSet(std::shared_ptr<CtxHandle> c, lm_hip_seqset *h) : ctx_(std::move(c)), h_(h) {}
+    ~SequenceSet() { lm_hip_seqset_destroy(h_); }
+    SequenceSet(SequenceSet &&o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_) { o.h_ = nullptr; }
+    SequenceSet(const SequenceSet &) = delete;
+
+    size_t records() const { return info().records; }
+    size_t total_length() const { return info().total; }
+    size_t rows() const { return info().rows; }
+    size_t wrap() const { return info().wrap; }
+    size_t columns() const { return info().cols; }
+    size_t len(size_t record) const
+    {
+        size_t n = 0;
+        check(lm_hip_seqset_record_length(h_, record, &n));
+        return n;
+    }
+    std::vector<size_t> lengths() const
+    {
+        std::vector<size_t> out(records());
+        if (!out.empty())
+            check(lm_hip_seqset_lengths(h_, out.data(), out.size()));
+        return out;
+    }
+    // seq.rs:369-381 on the set's matrix
+    void configure_wrap(size_t m) { check(lm_hip_seqset_configure_wrap(ctx_->ctx, h_, m)); }
+    lm_hip_seqset *handle() const { return h_; }
+
+private:
+    struct Info { size_t records, total, rows, wrap, cols, k; };
+    Info info() const
+    {
+        Info i{};
+        check(lm_hip_seqset_info(h_, &i.records, &i.total, &i.rows, &i.wrap, &i.cols, &i.k));
+        return i;
+    }
+    std::shared_ptr<CtxHandle> ctx_;
+    lm_hip_seqset *h_;
+};
+
 // ---- matrices (pwm/mod.rs) ---------------------------------------------------------------------
 
 template <class A>
@@ -1244,6 +1288,68 @@ public:
         }
         lm_hip_free(c);
         lm_hip_free(v);
+        return out;
+    }
+
+    // Many records -> one resident set (lm_hip_seqset_from_ascii): one upload, encode + stripe on the device.  Strict
+    // mode throws InvalidSymbol for the first byte outside the alphabet.
+    SequenceSet<A> stripe_set(const std::vector<std::string> &records, bool lossy = false, size_t columns = 32) const
+    {
+        std::string text;
+        std::vector<uint64_t> offsets(records.size() + 1, 0);
+        for (size_t r = 0; r < records.size(); ++r) {
+            text += records[r];
+            offsets[r + 1] = text.size();
+        }
+        lm_hip_seqset *h = nullptr;
+        size_t bad_record = 0, bad_index = 0;
+        const int st = lm_hip_seqset_from_ascii(ctx_->ctx, A::code, reinterpret_cast<const uint8_t *>(text.data()), text.size(),
+                                                offsets.data(), records.size(), columns, lossy ? 1 : 0, &h, &bad_record, &bad_index);
+        if (st == LM_HIP_ERR_INVALID_SYMBOL)
+            throw InvalidSymbol(records[bad_record][bad_index]);
+        check(st);
+        return SequenceSet<A>(ctx_, h);
+    }
+    // ... from encoded records (lm_hip_seqset_from_encoded)
+    SequenceSet<A> stripe_set(const std::vector<EncodedSequence<A>> &records, size_t columns = 32) const
+    {
+        std::vector<uint8_t> data;
+        std::vector<uint64_t> offsets(records.size() + 1, 0);
+        for (size_t r = 0; r < records.size(); ++r) {
+            data.insert(data.end(), records[r].data.begin(), records[r].data.end());
+            offsets[r + 1] = data.size();
+        }
+        lm_hip_seqset *h = nullptr;
+        check(lm_hip_seqset_from_encoded(ctx_->ctx, data.data(), data.size(), offsets.data(), records.size(), columns, A::K, &h));
+        return SequenceSet<A>(ctx_, h);
+    }
+    // Many motifs x every record of a set in one call (main.rs:502-561): per motif the hits with score >= thresholds[i]
+    // and position + M <= len(record) (scan.rs:185-190), ascending in (record, position).
+    struct SetHit {
+        size_t record, position;
+        float score;
+    };
+    std::vector<std::vector<SetHit>> scan_threshold(const std::vector<const ScoringMatrix<A> *> &pssms,
+                                                    const std::vector<float> &thresholds, const SequenceSet<A> &set) const
+    {
+        const size_t n = pssms.size();
+        if (thresholds.size() != n)
+            throw std::invalid_argument("one threshold per motif");
+        std::vector<const lm_hip_pssm *> handles(n);
+        for (size_t i = 0; i < n; ++i)
+            handles[i] = pssms[i]->device(ctx_->ctx);
+        std::vector<size_t> counts(n);
+        lm_hip_set_hit *h = nullptr;
+        check(lm_hip_scan_threshold_seqset(ctx_->ctx, handles.data(), thresholds.data(), n, set.handle(), counts.data(), &h));
+        std::vector<std::vector<SetHit>> out(n);
+        size_t pos = 0;
+        for (size_t i = 0; i < n; ++i) {
+            out[i].resize(counts[i]);
+            for (size_t k = 0; k < counts[i]; ++k)
+                out[i][k] = {h[pos + k].record, h[pos + k].position, h[pos + k].score};
+            pos += counts[i];
+        }
+        lm_hip_free(h);
         return out;
     }
 

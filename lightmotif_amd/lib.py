@@ -22,11 +22,11 @@ from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Un
 import numpy as np
 
 from . import _ffi
-from ._ffi import Coords, InvalidSymbol, LightmotifHipError, UnsupportedBackend, check
+from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, UnsupportedBackend, check
 
 __all__ = [
     "pack_2bit",
-    "Pipeline", "EncodedSequence", "StripedSequence", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "CountMatrix", "WeightMatrix",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -263,6 +263,65 @@ class Pipeline:
             raise InvalidSymbol(f"Invalid symbol in sequence: {chr(int(raw[bad.value]))!r}")
         check(st)
         return StripedSequence(self, h, protein)
+
+    def stripe_ascii_set(self, records: Sequence[Union[str, bytes, np.ndarray]], protein: bool = False, lossy: bool = False,
+                         columns: int = DEFAULT_COLUMNS, offsets: Optional[np.ndarray] = None) -> "StripedSequenceSet":
+        """Many records -> ONE resident striped sequence (their texts joined, no separators) plus the table of record
+        offsets: one upload, encode + stripe on the device (``lm_hip_seqset_from_ascii``).  ``records`` is a list of texts,
+        or ONE uint8 array holding the joined text together with ``offsets`` (``n + 1`` ascending positions, first 0)."""
+        if offsets is not None:
+            buf = np.ascontiguousarray(records, dtype=np.uint8)
+            offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        else:
+            raws = [r.tobytes() if isinstance(r, np.ndarray) else r.encode("ascii", "replace") if isinstance(r, str) else bytes(r)
+                    for r in records]
+            offs = np.zeros(len(raws) + 1, dtype=np.uint64)
+            np.cumsum([len(r) for r in raws], out=offs[1:])
+            buf = np.frombuffer(b"".join(raws), dtype=np.uint8)
+        if offs.ndim != 1 or offs.size == 0:
+            raise ValueError("offsets: one entry per record and one more")
+        h = C.c_void_p()
+        bad_r, bad_i = C.c_size_t(0), C.c_size_t(0)
+        st = self._L.lm_hip_seqset_from_ascii(self._h, b"P" if protein else b"D", buf.ctypes.data if buf.size else None, buf.size,
+                                              offs.ctypes.data, offs.size - 1, columns, int(lossy), C.byref(h), C.byref(bad_r),
+                                              C.byref(bad_i))
+        if st == _ffi.ERR_INVALID_SYMBOL:
+            byte = int(buf[int(offs[bad_r.value]) + bad_i.value])
+            raise InvalidSymbol(f"Invalid symbol in sequence {bad_r.value} at position {bad_i.value}: {chr(byte)!r}")
+        check(st)
+        return StripedSequenceSet(self, h, protein)
+
+    def stripe_set(self, encoded: Sequence["EncodedSequence"], columns: int = DEFAULT_COLUMNS) -> "StripedSequenceSet":
+        """The same from already encoded records (``lm_hip_seqset_from_encoded``)."""
+        protein = {e.protein for e in encoded}
+        if len(protein) > 1:
+            raise ValueError("the records of a set share one alphabet")
+        protein = bool(protein.pop()) if protein else False
+        parts = [np.ascontiguousarray(e.data, dtype=np.uint8) for e in encoded]
+        offs = np.zeros(len(parts) + 1, dtype=np.uint64)
+        np.cumsum([p.size for p in parts], out=offs[1:])
+        buf = np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)
+        h = C.c_void_p()
+        check(self._L.lm_hip_seqset_from_encoded(self._h, buf.ctypes.data if buf.size else None, buf.size, offs.ctypes.data,
+                                                 offs.size - 1, columns, _k(protein), C.byref(h)))
+        return StripedSequenceSet(self, h, protein)
+
+    def scan_threshold_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], thresholds: Optional[Sequence[float]],
+                           seqset: "StripedSequenceSet") -> "SetHits":
+        """``n`` motifs x every record of the set in one call (the CLI's whole job product, main.rs:502-561).  Per motif:
+        ``(records int64, positions int64, scores f32)`` with ``score >= t`` and ``position + M <= len(record)``
+        (scan.rs:185-190), ascending in (record, position) -- views cut from one block the library returned."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms, thresholds)
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        n = len(batch)
+        counts = np.zeros(n, dtype=np.uintp)
+        ptr = C.POINTER(SetHit)()
+        check(self._L.lm_hip_scan_threshold_seqset(self._h, batch.handles, batch.thresholds, n, seqset._h,
+                                                   counts.ctypes.data_as(C.POINTER(C.c_size_t)), C.byref(ptr)))
+        total = int(counts.sum())
+        raw = self._take_array(ptr, total * C.sizeof(SetHit), np.uint8)
+        return SetHits(raw.view(SET_HIT_DTYPE) if total else np.zeros(0, dtype=SET_HIT_DTYPE), counts)
 
     def upload(self, data: np.ndarray, length: int, wrap: int, columns: int,
                protein: bool = False) -> "StripedSequence":
@@ -689,6 +748,55 @@ class StripedSequence:
         return m if dtype is None else m.astype(dtype)
 
 
+class StripedSequenceSet:
+    """Many records resident as one striped sequence (``lm_hip_seqset``): ``len()`` = records."""
+
+    def __init__(self, pli: Pipeline, handle: C.c_void_p, protein: bool):
+        self._pli, self._h, self.protein = pli, handle, protein
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._pli._L.lm_hip_seqset_destroy(self._h)
+                self._h = None
+        except Exception:
+            pass
+
+    def _info(self):
+        v = [C.c_size_t(0) for _ in range(6)]
+        check(self._pli._L.lm_hip_seqset_info(self._h, *[C.byref(x) for x in v]))
+        return [x.value for x in v]
+
+    def __len__(self) -> int:
+        return self._info()[0]
+
+    @property
+    def total_length(self) -> int:
+        return self._info()[1]
+
+    @property
+    def rows(self) -> int:
+        return self._info()[2]
+
+    @property
+    def wrap(self) -> int:
+        return self._info()[3]
+
+    @property
+    def columns(self) -> int:
+        return self._info()[4]
+
+    @property
+    def lengths(self) -> np.ndarray:
+        out = np.zeros(len(self), dtype=np.uintp)
+        check(self._pli._L.lm_hip_seqset_lengths(self._h, out.ctypes.data, out.size))
+        return out.astype(np.int64)
+
+    def configure_wrap(self, m: int) -> None:
+        """seq.rs:369-381 on the set's matrix"""
+        check(self._pli._L.lm_hip_seqset_configure_wrap(self._pli._h, self._h, m))
+
+
 # --- matrices ------------------------------------------------------------------------
 
 
@@ -1017,6 +1125,36 @@ class BatchHits(Sequence):
             raise IndexError(i)
         a, b = int(self._starts[i]), int(self._starts[i + 1])
         return self.coords[a:b], self.values[a:b]
+
+    @property
+    def total(self) -> int:
+        return int(self._starts[-1])
+
+
+SET_HIT_DTYPE = np.dtype({"names": ["record", "position", "score"], "formats": [np.int64, np.int64, np.float32],
+                          "offsets": [0, 8, 16], "itemsize": C.sizeof(SetHit)})   # lm_hip_set_hit
+
+
+class SetHits(Sequence):
+    """The result of a scan over a sequence set: per motif ``(records int64, positions int64, scores f32)``, cut out of the
+    ONE array of ``lm_hip_set_hit`` the library returned when an element is asked for (as ``BatchHits``)."""
+
+    def __init__(self, hits: np.ndarray, counts: np.ndarray):
+        self.hits, self.counts = hits, counts
+        self._starts = np.concatenate(([0], np.cumsum(counts, dtype=np.int64)))
+
+    def __len__(self) -> int:
+        return len(self.counts)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        h = self.hits[int(self._starts[i]):int(self._starts[i + 1])]
+        return h["record"], h["position"], h["score"]
 
     @property
     def total(self) -> int:

@@ -9,11 +9,13 @@ Behaviour follows lightmotif-cli/src/main.rs:
   * every FASTA record is encoded lossily, striped and given ``max_m`` wrap rows
     (main.rs:540-546) -- here on the device, from the raw text;
   * the reference fans (motif, sequence) pairs out to worker threads (main.rs:554-561); here
-    all motifs of one record go to the GPU as ONE batched fused scan;
+    records are gathered into sets of up to ``--batch-bases`` bases, each set is resident as one
+    striped sequence, and all motifs x all records of a set go to the GPU as ONE call per strand
+    (``Pipeline.scan_threshold_set``: windows that leave their record are cut on the device);
   * output: TSV ``seq_index seq_name motif_index motif_name pos strand score pvalue`` with
     1-based indices and the p-value in exponent notation (main.rs:527-531, 587-600).
     The reference writes hits in worker-completion order; this driver writes them grouped by
-    sequence, then motif, then position.
+    sequence, then strand, then motif, then position.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -27,7 +29,9 @@ from typing import Iterator, List, Optional, Sequence, TextIO, Tuple
 import numpy as np
 
 from . import io as lmio
-from .lib import Pipeline, ScoringMatrix, StripedSequence
+from .lib import MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet
+
+DEFAULT_BATCH_BASES = 100_000_000
 
 
 def _open_text(path: str) -> TextIO:
@@ -88,6 +92,36 @@ def scan_record(pli: Pipeline, seq: StripedSequence, pssms: Sequence[ScoringMatr
     return out
 
 
+def batch_records(lengths: Sequence[int], budget: int) -> List[Tuple[int, int]]:
+    """Cuts a list of record lengths into consecutive sets ``[first, end)`` of at most ``budget`` bases each, in order,
+    every record in exactly one set.  A set is closed when the next record would take it over the budget -- unless it
+    holds no base yet, so a record larger than the budget stands alone (with the empty records right in front of it)
+    instead of being refused.  Empty records never close a set that still has room."""
+    if budget < 1:
+        raise ValueError("the base budget of a set must be positive")
+    sets, first, bases = [], 0, 0
+    for i, n in enumerate(lengths):
+        if bases > 0 and bases + n > budget:
+            sets.append((first, i))
+            first, bases = i, 0
+        bases += n
+    if first < len(lengths):
+        sets.append((first, len(lengths)))
+    return sets
+
+
+def scan_set(pli: Pipeline, seqset: StripedSequenceSet, batch: MotifBatch):
+    """All motifs x all records of a set: ``(record, motif, position, score)`` arrays ordered by record, then motif, then
+    position, and ``bounds`` with record r's hits at ``[bounds[r], bounds[r + 1])``."""
+    res = pli.scan_threshold_set(batch, None, seqset)
+    motif = np.repeat(np.arange(len(res), dtype=np.int64), np.asarray(res.counts, dtype=np.int64))
+    rec, pos, score = res.hits["record"], res.hits["position"], res.hits["score"]
+    order = np.argsort(rec, kind="stable")        # the list is (motif, record, position): a stable sort by record is all
+    rec = rec[order]
+    bounds = np.searchsorted(rec, np.arange(len(seqset) + 1))
+    return motif[order], pos[order], score[order], bounds
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
@@ -99,6 +133,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     group.add_argument("--rel-threshold", type=float)
     ap.add_argument("--reverse", action="store_true", help="also scan the reverse-complement matrices")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--batch-bases", type=int, default=DEFAULT_BATCH_BASES,
+                    help="bases of sequence gathered into one resident set and scanned with one call per strand "
+                         "(a longer record is a set of its own)")
     args = ap.parse_args(argv)
 
     print("Loading matrices")
@@ -114,23 +151,40 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         strands.append(("-", [p.reverse_complement() for p in direct]))
     max_m = max(lengths, default=0)
 
+    if args.batch_bases < 1:
+        ap.error("--batch-bases must be positive")
     pli = Pipeline.hip(args.device)
+    batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
     n_hits = 0
     with open(args.output, "w") as out, _open_text(args.sequences) as fasta:
         out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue\n")
-        for si, (name, text) in enumerate(read_fasta(fasta)):
-            seq = pli.stripe_ascii(text, lossy=True)
-            seq.configure_wrap(max_m)                                      # main.rs:543
-            for strand, pssms in strands:
-                for mi, (pos, scores) in enumerate(scan_record(pli, seq, pssms, thresholds)):
-                    if len(pos) == 0:
-                        continue
-                    dist = direct[mi].score_distribution                  # main.rs:335: motif.dist
-                    ident = records[mi].id
-                    for p, s in zip(pos.tolist(), scores.tolist()):
-                        out.write(f"{si + 1}\t{name}\t{mi + 1}\t{ident}\t{p}\t{strand}\t{_fmt_score(s)}\t"
+
+        def flush(first_index: int, names: List[str], texts: List[str]) -> int:
+            seqset = pli.stripe_ascii_set(texts, lossy=True)
+            seqset.configure_wrap(max_m)                                   # main.rs:543
+            found = [(strand, scan_set(pli, seqset, batch)) for strand, batch in batches]
+            wrote = 0
+            for r, name in enumerate(names):
+                for strand, (motif, pos, score, bounds) in found:
+                    a, b = int(bounds[r]), int(bounds[r + 1])
+                    for mi, p, s in zip(motif[a:b].tolist(), pos[a:b].tolist(), score[a:b].tolist()):
+                        dist = direct[mi].score_distribution              # main.rs:335: motif.dist
+                        out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{p}\t{strand}\t{_fmt_score(s)}\t"
                                   f"{_fmt_exp(dist.pvalue(s))}\n")
-                    n_hits += len(pos)
+                    wrote += b - a
+            return wrote
+
+        # the rule of batch_records, applied as the records stream in
+        first, names, texts, bases = 0, [], [], 0
+        for name, text in read_fasta(fasta):
+            if bases > 0 and bases + len(text) > args.batch_bases:
+                n_hits += flush(first, names, texts)
+                first, names, texts, bases = first + len(names), [], [], 0
+            names.append(name)
+            texts.append(text)
+            bases += len(text)
+        if names:
+            n_hits += flush(first, names, texts)
     print(f"Wrote {n_hits} hits to {args.output}")
     return 0
 

@@ -1,0 +1,170 @@
+#!/usr/bin/env python3
+"""Many motifs x many short records: what a resident sequence set saves over the per-record loop.
+
+Three ways to produce the same hit lists, timed on one MI355X in ONE process, alternating, after a warm-up:
+
+  A  the loop the CLI ran before sequence sets existed: per record ``stripe_ascii`` + ``configure_wrap`` +
+     ``scan_threshold_batch`` (prepared ``MotifBatch``) + the ``pos + M <= L`` cut and the sort on the host;
+  B  ``stripe_ascii_set`` + ``scan_threshold_set`` on the same records (one upload, one call, the cut on the device);
+  C  ``stripe_ascii`` + ``scan_threshold_batch`` on the plain concatenation: no segment pass, no offsets -- the floor
+     B cannot beat (its hit list is NOT the answer: it holds the windows that straddle records).
+
+Cases: (i) 2 000 records x 500 bp x 64 JASPAR motifs, (ii) 50 000 records x 200 bp x all 2 346 matrices of
+tests/golden/JASPAR2024.pwm.gz; thresholds at p = 1e-5.  Reports median and spread (min, max) of every way, the ratios
+A/B and B/C, the share of call C that its tail takes (re-score + order + host, ``lm_hip_ctx_last_phases_ms``), and the
+sustained shader clock.  ``python tools/seqset_bench.py [--case i|ii|both] [--runs 7] [--out profiles/seqset_bench.json]``
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+if str(ROOT) not in sys.path:
+    sys.path.insert(0, str(ROOT))
+
+import lightmotif_amd as lm  # noqa: E402
+from lightmotif_amd import io as lmio  # noqa: E402
+
+CASES = {"i": (2_000, 500, 64), "ii": (50_000, 200, None)}
+
+
+def load_motifs(count=None, pvalue=1e-5):
+    recs = list(lmio.read(ROOT / "tests" / "golden" / "JASPAR2024.pwm.gz"))
+    if count is not None:                         # spread over the file: all motif lengths take part
+        recs = [recs[i] for i in np.linspace(0, len(recs) - 1, count).astype(int)]
+    pssms = [r.matrix.normalize(0.1).log_odds() for r in recs]
+    return pssms, [p.score_for_pvalue(pvalue) for p in pssms]
+
+
+def make_records(n, length, seed=5):
+    rng = np.random.default_rng(seed)
+    text = np.frombuffer(b"ACGT", dtype=np.uint8)[rng.integers(0, 4, n * length)]
+    return [text[i * length:(i + 1) * length] for i in range(n)], text
+
+
+def run_loop(pli, records, batch, lengths, max_m):
+    """A: returns the number of hits (the lists are built and dropped, as the CLI consumes them record by record)."""
+    total = 0
+    for text in records:
+        seq = pli.stripe_ascii(text, lossy=True)
+        seq.configure_wrap(max_m)
+        rows, n = seq.rows, len(seq)
+        res = pli.scan_threshold_batch(batch, None, seq)
+        for (coords, values), m in zip(res, lengths):
+            pos = coords[:, 1] * rows + coords[:, 0]
+            keep = pos + m <= n
+            pos, values = pos[keep], values[keep]
+            order = np.argsort(pos, kind="stable")
+            pos, values = pos[order], values[order]
+            total += len(pos)
+    return total
+
+
+def run_set(pli, joined, offsets, batch, max_m):
+    """B"""
+    seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+    seqset.configure_wrap(max_m)
+    return pli.scan_threshold_set(batch, None, seqset).total
+
+
+def run_plain(pli, joined, batch, max_m):
+    """C"""
+    seq = pli.stripe_ascii(joined, lossy=True)
+    seq.configure_wrap(max_m)
+    return pli.scan_threshold_batch(batch, None, seq).total
+
+
+def timed(fn):
+    t0 = time.perf_counter()
+    n = fn()
+    return (time.perf_counter() - t0) * 1e3, n
+
+
+def measure(pli, n_records, length, n_motifs, runs=7, warmup=2, with_loop=True, loop_records=None):
+    """`loop_records`: A runs over the first so many records only and its time is scaled to all of them (the loop is
+    per record by construction; 50 000 records x 2 346 motifs spend minutes in its host code alone)."""
+    pssms, ts = load_motifs(n_motifs)
+    batch = pli.prepare_batch(pssms, ts)
+    lengths = [len(p) for p in pssms]
+    max_m = max(lengths)
+    records, joined = make_records(n_records, length)
+    offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(length)
+    ways = {"B": lambda: run_set(pli, joined, offsets, batch, max_m), "C": lambda: run_plain(pli, joined, batch, max_m)}
+    if with_loop:
+        ways["A"] = lambda: run_loop(pli, records[:loop_records] if loop_records else records, batch, lengths, max_m)
+    times = {k: [] for k in ways}
+    hits = {}
+    for it in range(warmup + runs):
+        for k in sorted(ways):                    # alternating: A, B, C, A, B, C ...
+            if k != "A":
+                # steady state: the library sizes a call's hit list and its ordering from the previous call on the
+                # context.  The CLI scans set after set of similar size; here the previous call would be the last tiny
+                # record of A (or the other way's list), so every timed B / C call follows an untimed one of its own kind
+                ways[k]()
+            ms, n = timed(ways[k])
+            hits[k] = n
+            if it >= warmup:
+                times[k].append(ms)
+    # the tail's share of call C, from the library's own phase clocks
+    pli.set_option("time_scan", 1)
+    run_plain(pli, joined, batch, max_m)
+    phases = pli.last_phases_ms
+    pli.set_option("time_scan", 0)
+    out = {"records": n_records, "record_length": length, "motifs": len(pssms), "runs": runs, "warmup": warmup, "hits": hits,
+           "ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "all": [round(x, 3) for x in v]}
+                  for k, v in times.items()}}
+    med = {k: out["ms"][k]["median"] for k in times}
+    if "A" in med and loop_records and loop_records < n_records:
+        out["A_measured_on_records"] = loop_records
+        out["A_scaled_median_ms"] = med["A"] * n_records / loop_records
+        med["A"] = out["A_scaled_median_ms"]
+    if "A" in med:
+        out["A_over_B"] = med["A"] / med["B"]
+    out["B_over_C"] = med["B"] / med["C"]
+    if phases and phases[0] >= 0:
+        tail = sum(max(x, 0.0) for x in phases[1:])
+        out["C_phases_ms"] = [round(float(x), 4) for x in phases]
+        out["C_tail_share"] = tail / (tail + phases[0]) if tail + phases[0] > 0 else None
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--case", default="both", choices=["i", "ii", "both"])
+    ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--runs-ii", dest="loop_runs_ii", type=int, default=5, help="runs of case (ii)")
+    ap.add_argument("--loop-records-ii", type=int, default=500, help="records the loop of case (ii) runs over (scaled to 50 000)")
+    ap.add_argument("--out", default=str(ROOT / "profiles" / "seqset_bench.json"))
+    a = ap.parse_args()
+    pli = lm.Pipeline.hip(0)
+    result = {"tool": "tools/seqset_bench.py", "device": "MI355X (gfx950)", "cases": {}}
+    for name in (["i", "ii"] if a.case == "both" else [a.case]):
+        n_records, length, n_motifs = CASES[name]
+        runs = a.runs if name == "i" else max(a.loop_runs_ii, 1)
+        warm = 2 if name == "i" else 1
+        res = measure(pli, n_records, length, n_motifs, runs=runs, warmup=warm, loop_records=a.loop_records_ii if name == "ii" else None)
+        result["cases"][name] = res
+        print(name, json.dumps({k: res[k] for k in ("A_over_B", "B_over_C", "C_tail_share", "hits") if k in res}), flush=True)
+    try:
+        joined = make_records(2_000, 500)[1]
+        pssms, ts = load_motifs(64)
+        batch = pli.prepare_batch(pssms, ts)
+        clock = pli.sustained_clock_mhz(lambda: run_plain(pli, joined, batch, max(len(p) for p in pssms)))
+        result["sustained_clock_mhz"] = clock if isinstance(clock, (int, float)) else list(clock) if clock is not None else None
+    except Exception as exc:  # a diagnostic: the timings stand without it
+        result["sustained_clock_mhz"] = f"unavailable: {exc}"
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps({"wrote": a.out}))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
