@@ -16,7 +16,7 @@
 #include <new>
 #include <string>
 
-#include "score_prefilter2.hpp"
+#include "score_registry.hpp"
 
 #include "lm_internal.hpp"
 
@@ -414,6 +414,8 @@ static int ctx_create(int device, void *stream, bool borrow, lm_hip_ctx **out)
     if (!out)
         return fail(LM_HIP_ERR_BAD_ARGS, "ctx_create: null output");
     *out = nullptr;
+    if (const char *hole = score_registry_hole())  // a unit the build compiles but the registry does not list (score_registry.hpp)
+        return fail(LM_HIP_ERR_HIP, "%s", hole);
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0)
         return fail(LM_HIP_ERR_NO_DEVICE, "no HIP device available");

@@ -218,7 +218,7 @@ struct lm_hip_pssm {
     unsigned *d_image2 = nullptr;  // DNA / protein: pair-symbol table of score_prefilter2.hpp (25 / 441 rows)
     // DNA, M = 20, 24, ... 36: the pair table of the first M - 1 rows.  The padded length of such a motif wastes a 16-byte
     // read per table row (M' = M + 3); a prefilter only has to over-estimate, so a single scan looks the first M - 1 rows up
-    // and credits the last row with its best weight, `drop_dmax` (score_threshold.hip: drop_last_form)
+    // and credits the last row with its best weight, `drop_dmax` (score_plan.hip: plan_scans, ScanPlan::drop)
     unsigned *d_image2_drop = nullptr;
     // DNA: the pair table in the layout the multi-motif passes of a batch read (8-byte LDS slots, score_prefilter2.hpp:
     // kDnaMulti); nullptr = those passes are not available for this matrix (the jobs run one motif per pass)

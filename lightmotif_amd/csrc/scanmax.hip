@@ -344,10 +344,9 @@ static int scan_max_by_list(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_h
     if (!ctx->list_scan_max || cols != 32 || seq->stride != 32 || k != 5 || m < 2 || m > (size_t)kMaxFastM || level < 1 || level > 255 ||
         (unsigned long long)rows * cols >= (1ull << 32) || reinterpret_cast<uintptr_t>(seq->d_data) % 4 != 0)
         return LM_HIP_OK;
-    PrefilterLauncher scan = score_c32_prefilter2_lookup((int)m, 5);
     ScoreArgs sa{nullptr, seq->d_data, seq->stride, cols, first_row, row_end, nullptr, cols};
     const C32Plan plan = plan_c32(ctx, MotifShape{m, k, true}, sa, false, 2, 1);
-    if (!scan || !plan.ok)
+    if (!score_c32_prefilter2_lookup((int)m, 5) || !plan.ok)
         return LM_HIP_OK;
     // the pair table and the dense copy of the u8 weights (host-packed, one small copy; the matrix of a Scanner changes per call)
     const size_t image_bytes = (size_t)prefilter2_image_dw((int)m) * 4, dense_bytes = (m * k + 15) / 16 * 16;
@@ -365,22 +364,15 @@ static int scan_max_by_list(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_h
     // low for this range, and the window walk is the better shape for it
     const unsigned long long cap = std::min<unsigned long long>(std::max<unsigned long long>(cells >> 12, 1ull << 14), 1ull << 18);
     const unsigned long long ccap = 2 * cap;
-    const size_t off_tables = 256, off_hits = off_tables + (image_bytes + dense_bytes + 255) / 256 * 256;
-    const size_t off_cands = off_hits + cap * sizeof(HitRecord);
-    LM_TRY(ctx->scratch.reserve(off_cands + ccap * sizeof(Candidate)));
-    char *base = static_cast<char *>(ctx->scratch.ptr);
+    const size_t off_tables = kHitListHead, off_hits = off_tables + (image_bytes + dense_bytes + 255) / 256 * 256;
     FusedOut fo{};
-    fo.hit_count = reinterpret_cast<unsigned long long *>(base);
-    fo.cand_count = fo.hit_count + 1;
-    fo.hits = reinterpret_cast<HitRecord *>(base + off_hits);
-    fo.hit_capacity = cap;
-    fo.cands = reinterpret_cast<Candidate *>(base + off_cands);
-    fo.cand_capacity = ccap;
+    char *base = nullptr;
+    LM_TRY(reserve_hit_lists(ctx, off_hits, cap, ccap, 0, &fo, &base));
     LM_HIP_TRY(hipMemsetAsync(base, 0, 16, ctx->stream));
     LM_HIP_TRY(hipMemcpyAsync(base + off_tables, stage.data(), stage.size(), hipMemcpyHostToDevice, ctx->stream));  // (pageable: copied out before the call returns)
     const unsigned *d_image = reinterpret_cast<const unsigned *>(base + off_tables);
     const uint8_t *d_dw = reinterpret_cast<const uint8_t *>(base + off_tables + image_bytes);
-    LM_HIP_TRY(scan(plan.grid, plan.lds, ctx->stream, seq->d_data, d_image, 5, first_row, row_end, plan.T, plan.nstreams, level, fo));
+    LM_TRY(launch_prefilter_scan(ctx, KIND_PREFILTER2, m, k, false, plan, ctx->stream, seq->d_data, first_row, row_end, d_image, level, fo));
     hipLaunchKernelGGL(scanmax_gate, dim3((unsigned)ctx->num_cus * 8), dim3(kBlock), 0, ctx->stream, fo, seq->d_data, pssm->d_dense, d_dw,
                        (unsigned)m, (unsigned)k, level, (unsigned long long)first_row);
     LM_HIP_TRY(hipGetLastError());

@@ -135,11 +135,8 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
     const std::vector<JobGroup> groups = group_jobs(ctx, jobs, n, [&](size_t i) {
         return plan_c32(ctx, jobs[i], false).ok ? KIND_EXACT : chunked_ok(ctx, jobs[i]) ? KIND_CHUNKED : KIND_GENERIC;
     });
-    ctx->last_scan_rows = ctx->last_scan_lds_bytes = 0;
-    if (n == 1 && groups.size() == 1 && groups[0].kind == KIND_EXACT) {
-        ctx->last_scan_rows = (unsigned)jobs[0].pssm->m;
-        ctx->last_scan_lds_bytes = scan_lds_bytes(KIND_EXACT, exact_motif(jobs[0].pssm, jobs[0].d_seq).m, jobs[0].pssm->k);
-    }
+    const ScanPlan sp = plan_scans(ctx, jobs, n, groups, false);  // (exact kernels only: nothing is padded or dropped)
+    record_scan_shape(ctx, sp, groups, jobs, n);
     std::vector<unsigned> grids(n);
     size_t total_blocks = 0;
     for (const JobGroup &g : groups)
@@ -182,25 +179,20 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
             pos += grids[i];
         }
     }
-    std::vector<BatchParams> bparams(n);
+    std::vector<BatchParams> bparams;  // in launch order: the jobs of a group are contiguous
     BatchParams *d_bparams = nullptr;
     if (n > 1) {
-        for (size_t i = 0; i < n; ++i)
-            bparams[i] = BatchParams{exact_motif(jobs[i].pssm, jobs[i].d_seq).table, blocks + block_pos[i], 0.0f, 0u, 0ull};
+        bparams.reserve(n);
+        for (size_t gi = 0; gi < groups.size(); ++gi)
+            for (size_t i : groups[gi].idx)
+                bparams.push_back(BatchParams{scan_table(sp, gi, groups[gi].kind, jobs[i]), blocks + block_pos[i], 0.0f, 0u, 0ull});
         LM_TRY(ctx->scratch2.reserve(sizeof(BatchParams) * n));
         d_bparams = static_cast<BatchParams *>(ctx->scratch2.ptr);
-    }
-    std::vector<BatchParams> ordered;  // in launch order: the jobs of a group are contiguous
-    ordered.reserve(n);
-    for (const JobGroup &g : groups)
-        for (size_t i : g.idx)
-            ordered.push_back(bparams[i]);
-    if (n > 1)
-        LM_HIP_TRY(hipMemcpyAsync(d_bparams, ordered.data(), sizeof(BatchParams) * n,
+        LM_HIP_TRY(hipMemcpyAsync(d_bparams, bparams.data(), sizeof(BatchParams) * n,
                                   hipMemcpyHostToDevice, ctx->stream));
-    const bool two_streams = groups.size() > 1;
-    if (two_streams)
-        LM_TRY(batch_fork(ctx));
+    }
+    BatchStreams streams(ctx, groups.size());
+    LM_TRY(streams.fork());
     // one job through the exact kernel: its last workgroup folds the records and writes the result straight
     // into the pinned block -- one launch instead of two (a small scan is launch-latency bound)
     const bool fold_in_kernel = n == 1 && groups.size() == 1 && groups[0].kind == KIND_EXACT && zero_copy;
@@ -208,10 +200,10 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
     unsigned host_nrec = 0;
     if (fold_in_kernel)
         LM_TRY(ensure_ticket(ctx));
-    size_t launch = 0, bp_pos = 0;
-    for (const JobGroup &g : groups) {
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const JobGroup &g = groups[gi];
         const ScoreArgs &a = jobs[g.idx[0]];
-        hipStream_t st = (two_streams && (launch++ & 1)) ? ctx->aux_stream : ctx->stream;
+        hipStream_t st = streams.next();
         FusedOut fo{};
         fo.block_best = blocks + block_pos[g.idx[0]];
         if (fold_in_kernel) {
@@ -235,13 +227,8 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
             }
         }
         if (g.kind == KIND_EXACT) {
-            fo.batch = n > 1 ? d_bparams + bp_pos : nullptr;
-            const ExactMotif em = exact_motif(a.pssm, a.d_seq);  // (a group shares length, hence padding)
-            fo.lead_rows = em.lead;
-            ScoreC32Launcher fn = score_c32_lookup((int)em.m, MODE_ARGMAX, lds_wide((int)a.pssm->k));
-            ctx->last_kernel = score_c32_name((int)em.m, MODE_ARGMAX);
-            LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, st, a.d_seq, em.table, (int)a.pssm->k,
-                          a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, nullptr, fo));
+            fo.batch = n > 1 ? d_bparams + sp.groups[gi].pos : nullptr;
+            LM_TRY(launch_group_scan(ctx, sp, gi, g, a, MODE_ARGMAX, 0u, st, fo));
         } else if (g.kind == KIND_CHUNKED) {
             // (always on ctx->stream: the chunk buffer is shared)
             const unsigned cg = chunk_argmax_grid(ctx);
@@ -255,7 +242,6 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
             ctx->last_kernel = "score_generic<1>";
             LM_TRY(launch_generic<MODE_ARGMAX>(ctx, a, fo, dim3(grids[g.idx[0]]), st));
         }
-        bp_pos += g.idx.size();
     }
     for (size_t i = 0; i < n; ++i) {
         const ScoreArgs &a = jobs[i];
@@ -263,8 +249,7 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
                             a.d_seq + a.row_begin * a.seq_stride,
                             (unsigned long long)a.seq_stride, a.pssm->d_dense};
     }
-    if (two_streams)
-        LM_TRY(batch_join(ctx));
+    LM_TRY(streams.join());
     if (!zero_copy)
         LM_HIP_TRY(hipMemcpyAsync(d_jobs, fj, sizeof(FinalizeJob) * n, hipMemcpyHostToDevice,
                                   ctx->stream));
@@ -659,157 +644,70 @@ static int argmax_by_prefilter(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
         return (ctx->pair_prefilter && plan_c32(ctx, qjobs[q], false, 2).ok) ? (int)KIND_PREFILTER2
                                                                              : (int)KIND_PREFILTER;
     });
-    std::vector<char> pairs_of(nq, 0);
-    for (const JobGroup &g : groups)
-        for (size_t q : g.idx)
-            pairs_of[q] = g.kind == KIND_PREFILTER2;
-    // a lone pair scan of M = 20, 24, ... 36 rows: the drop-last form (score_threshold.hip, lm_hip_pssm::d_image2_drop)
-    C32Plan drop_plan;
-    if (nq == 1 && groups.size() == 1 && groups[0].kind == KIND_PREFILTER2 && ctx->drop_last && qjobs[0].pssm->d_image2_drop &&
-        score_c32_prefilter2_lookup((int)qjobs[0].pssm->m - 1, (int)qjobs[0].pssm->k))
-        drop_plan = plan_c32(ctx, MotifShape{qjobs[0].pssm->m - 1, qjobs[0].pssm->k, true}, qjobs[0], false, 2, 1);
-    const bool drop_last_form = drop_plan.ok;
-    if (drop_last_form)
+    // (drop-last form of a lone pair scan: argmax_prepare declines on the device when the unscanned row carries too much)
+    const ScanPlan sp = plan_scans(ctx, qjobs.data(), nq, groups, true);
+    if (sp.drop.ok)
         sjobs[0].td_drop = qjobs[0].pssm->drop_dmax;
-    ctx->last_scan_rows = ctx->last_scan_lds_bytes = 0;
-    if (nq == 1 && groups.size() == 1) {
-        const size_t scanned = qjobs[0].pssm->m - (drop_last_form ? 1 : 0);
-        ctx->last_scan_lds_bytes = scan_lds_bytes(groups[0].kind, scanned, qjobs[0].pssm->k);
-        ctx->last_scan_rows = (unsigned)scanned;
-    }
-    std::vector<BatchParams> bparams;  // launch order; rjobs / sjobs are permuted the same way
-    // positions in launch order; groups of the pair scan with several jobs run `per_pass[g]`
-    // motifs per pass and are padded to a multiple of that (a padding position samples nothing,
-    // so argmax_prepare leaves its td at "skip" and it flags nothing)
-    std::vector<size_t> order, group_pos(groups.size());
-    std::vector<char> is_pad, in_multi;  // in_multi: the position's group runs several motifs per pass (tables in that kernel's layout)
-    std::vector<int> per_pass(groups.size(), 1);
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const JobGroup &g = groups[gi];
-        group_pos[gi] = order.size();
-        for (size_t q : g.idx) {
-            order.push_back(q);
-            is_pad.push_back(0);
-        }
-        const int m = (int)qjobs[g.idx[0]].pssm->m;
-        bool multi = g.kind == KIND_PREFILTER2 && ctx->multi_motif && g.idx.size() >= 2 && qjobs[g.idx[0]].pssm->k == 5 &&
-                     score_c32_prefilter2_multi_lookup(m);
-        for (size_t q : g.idx)  // (every matrix of the group needs its table in that kernel's layout)
-            multi = multi && qjobs[q].pssm->d_image2_multi != nullptr;
-        if (multi) {
-            per_pass[gi] = prefilter2_multi(m);
-            while ((order.size() - group_pos[gi]) % per_pass[gi]) {
-                order.push_back(g.idx.back());
-                is_pad.push_back(1);
-            }
-        }
-        in_multi.resize(order.size(), multi ? 1 : 0);
-    }
-    const size_t npos = order.size();
+    record_scan_shape(ctx, sp, groups, qjobs.data(), nq);
+    // the three job tables in launch order; a padding position samples nothing, so argmax_prepare leaves its td at "skip"
+    const size_t npos = sp.order.size();
     std::vector<SampleJob> sj(npos);
     std::vector<RescoreJob> rj(npos);
-    for (size_t pos = 0; pos < npos; ++pos) {
-        const size_t q = order[pos];
-        sj[pos] = sjobs[q];
-        if (is_pad[pos])
-            sj[pos].nchunks = 0;
-        rj[pos] = rjobs[q];
-        bparams.push_back(BatchParams{drop_last_form ? qjobs[q].pssm->d_image2_drop
-                                      : in_multi[pos] ? qjobs[q].pssm->d_image2_multi
-                                      : pairs_of[q]  ? qjobs[q].pssm->d_image2
-                                                     : qjobs[q].pssm->d_image,
-                                      nullptr, 0.0f, 0xffffffffu, (unsigned long long)pos << 40});
-    }
+    std::vector<BatchParams> bparams(npos);
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        for (size_t pos = sp.groups[gi].pos; pos < sp.group_end(gi); ++pos) {
+            const size_t q = sp.order[pos].job;
+            sj[pos] = sjobs[q];
+            if (sp.order[pos].pad)
+                sj[pos].nchunks = 0;
+            rj[pos] = rjobs[q];
+            bparams[pos] = BatchParams{scan_table(sp, gi, groups[gi].kind, qjobs[q]), nullptr, 0.0f, 0xffffffffu,
+                                       (unsigned long long)pos << 40};
+        }
     // ~1024 cells tie with or beat the bound of a 1/1024 sample; leave room for 8x that
     // (bounded at 32 M / 128 M records = 2.5 GB for very large batches: lists that overflow send
     // the batch to the exact kernel, they never change a result)
     const unsigned long long cap = std::min<unsigned long long>(npos * 8192 + (1 << 16), 32ull << 20),
                              ccap = 4 * cap;
-    // layout: the head -- counters | sample bounds | best values | best keys | the three job tables --
-    // is assembled in the upper half of the pinned buffer and reaches the device as ONE copy
-    // (three memsets and three staged copies from pageable memory cost more than the sample pass)
+    // head of the scratch block: counters | best values | best keys | the three job tables (| results, not sent); tail: the sample's maxima
     const unsigned sgrid = (unsigned)std::min<unsigned long long>(
         max_chunks, std::max<unsigned long long>((unsigned long long)ctx->num_cus * 8 / npos, 16));
-    const size_t off_bval = 256;  // the counters keep their cache lines to themselves
+    const size_t off_bval = kHitListHead;
     const size_t off_bkey = (off_bval + npos * 4 + 15) / 16 * 16;
     const size_t off_rj = off_bkey + npos * 8;
     const size_t off_bp = off_rj + (npos * sizeof(RescoreJob) + 15) / 16 * 16;
     const size_t off_sj = off_bp + (npos * sizeof(BatchParams) + 15) / 16 * 16;
     const size_t off_res = off_sj + (npos * sizeof(SampleJob) + 15) / 16 * 16;
     const size_t off_hits = off_res + npos * sizeof(ArgmaxRecord);
-    const size_t off_cands = off_hits + cap * sizeof(HitRecord);
-    const size_t off_partial = off_cands + ccap * sizeof(Candidate);  // the sample's per-workgroup maxima
-    LM_TRY(ctx->scratch.reserve(off_partial + npos * sgrid * sizeof(unsigned)));
-    char *base = static_cast<char *>(ctx->scratch.ptr);
     FusedOut fo{};
-    fo.hit_count = reinterpret_cast<unsigned long long *>(base);
-    fo.cand_count = fo.hit_count + 1;
-    unsigned *d_partial = reinterpret_cast<unsigned *>(base + off_partial);
+    char *base = nullptr;
+    LM_TRY(reserve_hit_lists(ctx, off_hits, cap, ccap, npos * sgrid * sizeof(unsigned), &fo, &base));
+    unsigned *d_partial = reinterpret_cast<unsigned *>(fo.cands + ccap);
     unsigned *d_bval = reinterpret_cast<unsigned *>(base + off_bval);
     unsigned long long *d_bkey = reinterpret_cast<unsigned long long *>(base + off_bkey);
-    fo.hits = reinterpret_cast<HitRecord *>(base + off_hits);
-    fo.hit_capacity = cap;
-    fo.cands = reinterpret_cast<Candidate *>(base + off_cands);
-    fo.cand_capacity = ccap;
     RescoreJob *d_rj = reinterpret_cast<RescoreJob *>(base + off_rj);
     BatchParams *d_bp = reinterpret_cast<BatchParams *>(base + off_bp);
     SampleJob *d_sj = reinterpret_cast<SampleJob *>(base + off_sj);
     ArgmaxRecord *d_res = reinterpret_cast<ArgmaxRecord *>(base + off_res);
     hipStream_t st = ctx->stream;
-    if (off_res <= kPinnedBytes / 2) {
-        char *head = static_cast<char *>(ctx->pinned) + kPinnedBytes / 2;
-        memset(head, 0, off_rj);
-        for (size_t q = 0; q < npos; ++q)  // best values start at -inf
-            reinterpret_cast<unsigned *>(head + off_bval)[q] = kOrderedNegInf;
-        memcpy(head + off_rj, rj.data(), npos * sizeof(RescoreJob));
-        memcpy(head + off_bp, bparams.data(), npos * sizeof(BatchParams));
-        memcpy(head + off_sj, sj.data(), npos * sizeof(SampleJob));
-        LM_HIP_TRY(hipMemcpyAsync(base, head, off_res, hipMemcpyHostToDevice, st));
-    } else {
-        LM_HIP_TRY(hipMemsetAsync(base, 0, 16, st));
-        LM_HIP_TRY(hipMemsetAsync(d_bkey, 0, npos * 8, st));
-        LM_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_bval), (int)kOrderedNegInf, npos, st));
-        LM_HIP_TRY(hipMemcpyAsync(d_rj, rj.data(), npos * sizeof(RescoreJob), hipMemcpyHostToDevice, st));
-        LM_HIP_TRY(hipMemcpyAsync(d_bp, bparams.data(), npos * sizeof(BatchParams), hipMemcpyHostToDevice, st));
-        LM_HIP_TRY(hipMemcpyAsync(d_sj, sj.data(), npos * sizeof(SampleJob), hipMemcpyHostToDevice, st));
-    }
+    const HeadPart parts[5] = {{off_bval, nullptr, npos * 4, kOrderedNegInf},  // best values start at -inf,
+                               {off_bkey, nullptr, npos * 8, 0u},             // best keys at zero
+                               {off_rj, rj.data(), npos * sizeof(RescoreJob), 0u},
+                               {off_bp, bparams.data(), npos * sizeof(BatchParams), 0u},
+                               {off_sj, sj.data(), npos * sizeof(SampleJob), 0u}};
+    LM_TRY(upload_head(ctx, st, base, off_res, off_rj, parts, 5));
     hipLaunchKernelGGL(argmax_sample, dim3(sgrid, (unsigned)npos), dim3(kBlock), 0, st, d_sj, d_partial);
     hipLaunchKernelGGL(argmax_prepare, dim3((unsigned)npos), dim3(64), 0, st, d_sj, (unsigned)npos, d_partial, sgrid,
                        d_rj, d_bp);
     LM_HIP_TRY(hipGetLastError());
-    const bool two_streams = groups.size() > 1;
+    BatchStreams streams(ctx, groups.size());
     scan_timer_begin(ctx, st);
-    if (two_streams)
-        LM_TRY(batch_fork(ctx));
-    size_t launch = 0;
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const JobGroup &g = groups[gi];
-        const ScoreArgs &a = qjobs[g.idx[0]];
-        hipStream_t ls = (two_streams && (launch++ & 1)) ? ctx->aux_stream : st;
-        fo.batch = d_bp + group_pos[gi];
-        if (per_pass[gi] > 1) {  // several motifs of this length per pass over the sequence
-            dim3 grid = g.plan.grid;
-            grid.y = (unsigned)((g.idx.size() + per_pass[gi] - 1) / per_pass[gi]);
-            ctx->last_kernel = "score_c32_prefilter2_multi";
-            LM_HIP_TRY(score_c32_prefilter2_multi_lookup((int)a.pssm->m)(grid, ls, a.d_seq, a.row_begin, a.row_end,
-                                                                        g.plan.T, g.plan.nstreams, fo));
-            continue;
-        }
-        const bool pairs = g.kind == KIND_PREFILTER2;
-        ctx->last_kernel = pairs ? "score_c32_prefilter2" : block_scan(ctx, a) ? "score_c32_prefilter_blk" : "score_c32_prefilter";
-        if (drop_last_form) {  // (table and threshold come from the job's BatchParams)
-            PrefilterLauncher fn = score_c32_prefilter2_lookup((int)a.pssm->m - 1, (int)a.pssm->k);
-            LM_HIP_TRY(fn(drop_plan.grid, drop_plan.lds, ls, a.d_seq, a.pssm->d_image2_drop, (int)a.pssm->k, a.row_begin, a.row_end,
-                          drop_plan.T, drop_plan.nstreams, 0xffffffffu, fo));
-            continue;
-        }
-        PrefilterLauncher fn = pairs ? score_c32_prefilter2_lookup((int)a.pssm->m, (int)a.pssm->k)
-                                     : score_c32_prefilter_lookup((int)a.pssm->m, lds_wide((int)a.pssm->k), block_scan(ctx, a));
-        LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, ls, a.d_seq, pairs ? a.pssm->d_image2 : a.pssm->d_image,
-                      (int)a.pssm->k, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, 0xffffffffu, fo));
+    LM_TRY(streams.fork());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {  // (tables and thresholds come from the jobs' BatchParams)
+        fo.batch = d_bp + sp.groups[gi].pos;
+        LM_TRY(launch_group_scan(ctx, sp, gi, groups[gi], qjobs[groups[gi].idx[0]], MODE_THRESHOLD, 0xffffffffu, streams.next(), fo));
     }
-    if (two_streams)
-        LM_TRY(batch_join(ctx));
+    LM_TRY(streams.join());
     scan_timer_end(ctx, st);
     fo.batch = nullptr;
     LM_TRY(launch_rescore(ctx, st, d_rj, fo, rj.data(), npos));
@@ -846,7 +744,7 @@ static int argmax_by_prefilter(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
     const ArgmaxRecord *r = pin ? res : host_res.data();
     for (size_t pos = 0; pos < npos; ++pos)
         if (r[pos].found) {
-            const size_t i = pick[order[pos]];
+            const size_t i = pick[sp.order[pos].job];
             out[i] = r[pos];
             done[i] = 1;
         }

@@ -1,7 +1,7 @@
 // score_inst.hip -- instantiates score_c32<M, MODE> for M in [LM_M_LO, LM_M_HI].
 // Compiled several times with different -DLM_M_LO/-DLM_M_HI/-DLM_INST_ID so the
 // fully unrolled kernels build in parallel (see build.py).
-#include "score_u8.hpp"
+#include "score_registry.hpp"
 
 #ifndef LM_M_LO
 #error "LM_M_LO / LM_M_HI / LM_INST_ID must be defined"
@@ -9,8 +9,21 @@
 
 namespace lm {
 
-#define LM_CAT2(a, b) a##b
-#define LM_CAT(a, b) LM_CAT2(a, b)
+// the exact f32 kernels of one length for one alphabet width (WIDE: more than 16 symbols, 8-byte LDS reads)
+template <int M, int WIDE>
+static void fill_c32_row(ScoreC32Launcher *tab)
+{
+    tab[SLOT_STORE] = &score_c32_launch<M, MODE_STORE, 0, 32, WIDE>;
+    tab[SLOT_ARGMAX] = &score_c32_launch<M, MODE_ARGMAX, 0, 32, WIDE>;
+    tab[SLOT_THRESHOLD] = &score_c32_launch<M, MODE_THRESHOLD, 0, 32, WIDE>;
+    if constexpr (M % 4 == 0) {
+        tab[SLOT_STORE_QL] = &score_c32_launch<M, MODE_STORE, 1, 32, WIDE>;
+        tab[SLOT_STORE_C16] = &score_c32_launch<M, MODE_STORE, 1, 16, WIDE>;
+        tab[SLOT_STORE_TRACK] = &score_c32_launch<M, MODE_STORE_TRACK, 1, 32, WIDE>;
+    }
+    tab[SLOT_STORE_ARGMAX] = &score_c32_launch<M, MODE_STORE_ARGMAX, 1, 32, WIDE>;
+    tab[SLOT_CONTINUE] = &score_c32_launch<M, MODE_CONTINUE, 1, 32, WIDE>;
+}
 
 template <int M>
 struct RegisterRange {
@@ -25,32 +38,12 @@ struct RegisterRange {
             if constexpr (prefilter2_multi(M) > 1)
                 r.pre2_multi[M] = &score_c32_prefilter2_multi_launch<M>;
         }
-        ScoreC32Launcher *tab = r.c32[M];
-        tab[MODE_STORE] = &score_c32_launch<M, MODE_STORE>;
-        tab[MODE_ARGMAX] = &score_c32_launch<M, MODE_ARGMAX>;
-        tab[MODE_THRESHOLD] = &score_c32_launch<M, MODE_THRESHOLD>;
-        if constexpr (M % 4 == 0) {
-            tab[7] = &score_c32_launch<M, MODE_STORE, 1>;
-            tab[10] = &score_c32_launch<M, MODE_STORE, 1, 16>;
-            tab[11] = &score_c32_launch<M, MODE_STORE_TRACK, 1>;
-        }
-        tab[8] = &score_c32_launch<M, MODE_STORE_ARGMAX, 1>;
-        tab[9] = &score_c32_launch<M, MODE_CONTINUE, 1>;
-        // wide alphabets (protein): the slots the launchers use at C = 32
+        fill_c32_row<M, 0>(r.c32[M]);
+        // wide alphabets (protein)
         r.prew[M] = &score_c32_prefilter_launch<M, 1>;
         r.preblk[M] = &score_c32_prefilter_blk_launch<M>;
         r.u8w[M] = &score_c32_u8_launch<M, 1>;
-        ScoreC32Launcher *tw = r.c32w[M];
-        tw[MODE_STORE] = &score_c32_launch<M, MODE_STORE, 0, 32, 1>;
-        tw[MODE_ARGMAX] = &score_c32_launch<M, MODE_ARGMAX, 0, 32, 1>;
-        tw[MODE_THRESHOLD] = &score_c32_launch<M, MODE_THRESHOLD, 0, 32, 1>;
-        if constexpr (M % 4 == 0) {
-            tw[7] = &score_c32_launch<M, MODE_STORE, 1, 32, 1>;
-            tw[10] = &score_c32_launch<M, MODE_STORE, 1, 16, 1>;
-            tw[11] = &score_c32_launch<M, MODE_STORE_TRACK, 1, 32, 1>;
-        }
-        tw[8] = &score_c32_launch<M, MODE_STORE_ARGMAX, 1, 32, 1>;
-        tw[9] = &score_c32_launch<M, MODE_CONTINUE, 1, 32, 1>;
+        fill_c32_row<M, 1>(r.c32w[M]);
         if constexpr (M < LM_M_HI)
             RegisterRange<M + 1>::run(r);
     }

@@ -99,6 +99,11 @@ __device__ __forceinline__ void lds_zero_based(const void *dynamic_lds)
 // cell located afterwards) stays the large-input form: index tracking costs the store kernel 15 %.
 enum : int { MODE_STORE = 0, MODE_ARGMAX = 1, MODE_THRESHOLD = 2, MODE_STORE_ARGMAX = 3, MODE_CONTINUE = 4,
              MODE_STORE_TRACK = 5 };
+// Rows of the launcher registry (score_registry.hpp): the three modes every length has under their MODE_* value, then the
+// store kernel with quad-gathered (dword) symbol loads (M % 4 == 0), store + running maximum (score_into on handles),
+// MODE_CONTINUE, the store kernel for C = 16 (M % 4 == 0, M <= kMaxFastM), MODE_STORE_TRACK (M % 4 == 0: small score_into + argmax)
+enum : int { SLOT_STORE = MODE_STORE, SLOT_ARGMAX = MODE_ARGMAX, SLOT_THRESHOLD = MODE_THRESHOLD, SLOT_STORE_QL,
+             SLOT_STORE_ARGMAX, SLOT_CONTINUE, SLOT_STORE_C16, SLOT_STORE_TRACK, kRegistrySlots };
 constexpr bool mode_stores(int mode)
 {
     return mode == MODE_STORE || mode == MODE_STORE_ARGMAX || mode == MODE_CONTINUE || mode == MODE_STORE_TRACK;
@@ -1121,7 +1126,7 @@ __global__ __launch_bounds__(kBlock) void score_continue_cells(
     }
 }
 
-// Host-side launch shim, one per (M, MODE), defined in score_inst_*.hip.
+// Host-side launch shim, one per (M, MODE), instantiated by the score_*_inst.hip units (score_registry.hpp).
 using ScoreC32Launcher = hipError_t (*)(dim3 grid, size_t lds_bytes, hipStream_t stream,
                                         const uint8_t *seq, const float *table, int K,
                                         unsigned long long row_begin, unsigned long long row_end,
@@ -1138,20 +1143,5 @@ hipError_t score_c32_launch(dim3 grid, size_t lds_bytes, hipStream_t stream, con
                        row_begin, row_end, T, nstreams, out, fo);
     return hipGetLastError();
 }
-
-// Filled by the score_inst_*.hip translation units; [M][MODE], nullptr if absent.
-// Registry row: [0..2] = modes, [3..6] = unused, [7] = store kernel with quad-gathered symbol
-// loads (M % 4 == 0), [8] = store + running maximum (score_into on handles).
-constexpr int kRegistrySlots = 12;  // [9] = MODE_CONTINUE (later passes of motifs longer than kMaxFastM),
-                                    // [10] = store kernel for C = 16 (M % 4 == 0, quad loads),
-                                    // [11] = MODE_STORE_TRACK (M % 4 == 0, quad loads): small score_into + argmax
-// `wide`: the kernels for alphabets of more than 16 symbols (lds_wide(K): 8-byte LDS reads)
-ScoreC32Launcher score_c32_lookup(int M, int mode, bool wide = false);
-ScoreC32Launcher score_c32_lookup_ql(int M, bool wide = false);
-ScoreC32Launcher score_c32_lookup_store_argmax(int M, bool wide = false);
-ScoreC32Launcher score_c32_lookup_continue(int M, bool wide = false);
-ScoreC32Launcher score_c32_lookup_c16(int M, bool wide = false);
-ScoreC32Launcher score_c32_lookup_store_track(int M, bool wide = false);
-const char *score_c32_name(int M, int mode);
 
 }  // namespace lm

@@ -1,6 +1,7 @@
-// score_launch.hpp -- what the launch code of the scoring kernels shares between its translation units
-// (score_plan.hip: registry + stream geometry; score_store.hip: Score into a matrix; score_argmax.hip and
-// score_threshold.hip: the fused Maximum / Threshold routes).  Kernel bodies: score_kernels.hpp.
+// score_launch.hpp -- what the launch code of the scoring kernels (score_store.hip, score_argmax.hip, score_threshold.hip,
+// scanmax.hip) shares, defined in score_plan.hip: the kernel registry (score_registry.hpp), the stream geometry (plan_c32),
+// and what the fused routes have in common -- the scans of a batch and their launch (ScanPlan, launch_group_scan), stream
+// alternation (BatchStreams), the hit lists' scratch layout and a call's head upload.  Kernel bodies: score_kernels.hpp.
 #pragma once
 
 #include <algorithm>
@@ -8,15 +9,9 @@
 #include <tuple>
 #include <vector>
 
-#include "score_prefilter2.hpp"
-#include "score_u8.hpp"
+#include "score_registry.hpp"
 
 namespace lm {
-
-// ---- registry look-ups defined with the registry (score_plan.hip; the others are declared next to their kernels) ----
-
-ScoreU8Launcher score_c32_lookup_u8(int M, bool pairs, bool wide);
-PrefilterMultiLauncher score_c32_prefilter2_multi_lookup(int M);
 
 // ---- stream geometry (score_plan.hip) -------------------------------------------------------------------
 
@@ -86,13 +81,19 @@ int launch_generic(lm_hip_ctx *ctx, const ScoreArgs &a, const FusedOut &fo, dim3
 
 // ---- batches (score_plan.hip) -----------------------------------------------------------------------------
 
-// Enqueues the fused argmax of one job: block records -> `blocks`, result -> `d_result`.
-// Independent jobs of a batch alternate between the context's stream and an auxiliary
-// one, so the tail of one motif's kernel (the last, partially filled round of
-// workgroups) overlaps the head of the next.  fork: aux waits for everything already
-// enqueued on the main stream; join: the main stream waits for aux.
-int batch_fork(lm_hip_ctx *ctx);
-int batch_join(lm_hip_ctx *ctx);
+// Independent groups of a batch alternate between the context's stream and an auxiliary one, so the tail of one motif's
+// kernel (the last, partially filled round of workgroups) overlaps the head of the next.  fork (more than one group only):
+// aux waits for everything already enqueued on the main stream; join: the main stream waits for aux.
+// (KIND_CHUNKED work ignores what next() hands out and stays on ctx->stream: the chunk buffer is shared.)
+struct BatchStreams {
+    lm_hip_ctx *ctx;
+    bool two;
+    size_t launch = 0;
+    BatchStreams(lm_hip_ctx *c, size_t ngroups) : ctx(c), two(ngroups > 1) {}
+    int fork();
+    hipStream_t next() { return (two && (launch++ & 1)) ? ctx->aux_stream : ctx->stream; }
+    int join();
+};
 
 // Jobs of a batch that can share ONE launch (grid.y = jobs): same kernel, motif length,
 // alphabet and sequence rows.  Many short per-motif launches lose ~15 % to their ramps
@@ -155,6 +156,55 @@ std::vector<JobGroup> group_jobs(const lm_hip_ctx *ctx, const ScoreArgs *jobs, s
         }
     return groups;
 }
+
+// ---- the scans of a batch (score_plan.hip) --------------------------------------------------------------------
+// Computed once from the JobGroups of a call.  Launch order: the jobs of a group are contiguous from ScanGroup::pos on.  A
+// group of the DNA pair scan with several jobs runs `per_pass` motifs per pass (score_c32_prefilter2_multi) and is padded to
+// a multiple of that with repeats of its last job (Pos::pad), which the caller makes harmless in its job table.
+struct ScanGroup {
+    bool multi = false;  // several motifs per pass: every matrix of the group has its table in that kernel's layout
+    int per_pass = 1;
+    size_t pos = 0;      // first position of the group in launch order
+};
+struct ScanPlan {
+    struct Pos { size_t job; bool pad; };
+    std::vector<ScanGroup> groups;  // one per JobGroup
+    std::vector<Pos> order;
+    // One pair scan of a motif of M = 20, 24, ... 36 rows: its first M - 1 rows are looked up and the last row is credited with
+    // its best weight (lm_hip_pssm::d_image2_drop) -- table rows of one 16-byte read less, up to four times the candidate
+    // pieces, identical hits (every candidate is re-scored over all M rows).  drop.ok: the call's one scan takes this form.
+    C32Plan drop;
+    size_t group_end(size_t gi) const { return gi + 1 < groups.size() ? groups[gi + 1].pos : order.size(); }
+};
+// `allow_drop`: what the route adds to the drop-last rule (the threshold route declines when the last row carries a large
+// part of the threshold: the scan would flag too much)
+ScanPlan plan_scans(const lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n, const std::vector<JobGroup> &groups, bool allow_drop);
+// the table a job's BatchParams points at: drop / multi / pair / one-symbol image, or the exact kernel's table
+const void *scan_table(const ScanPlan &sp, size_t gi, int kind, const ScoreArgs &a);
+// ctx->last_scan_rows / last_scan_lds_bytes: the shape of a call's ONE scan (zero for batches and the generic routes)
+void record_scan_shape(lm_hip_ctx *ctx, const ScanPlan &sp, const std::vector<JobGroup> &groups, const ScoreArgs *jobs, size_t n);
+// one prefilter scan (KIND_PREFILTER / KIND_PREFILTER2; `blocks`: block_scan) over `m` motif rows with the table at `image`
+int launch_prefilter_scan(lm_hip_ctx *ctx, int kind, size_t m, size_t k, bool blocks, const C32Plan &plan, hipStream_t st,
+                          const uint8_t *d_seq, size_t row_begin, size_t row_end, const unsigned *image, unsigned td,
+                          const FusedOut &fo);
+// the launch of group `gi` (`a`: its first job): multi-motif kernel, drop-last form, pair or one-symbol scan (`td`: their
+// threshold when fo.batch is null) or the exact kernel in `mode`; both set ctx->last_kernel
+int launch_group_scan(lm_hip_ctx *ctx, const ScanPlan &sp, size_t gi, const JobGroup &g, const ScoreArgs &a, int mode, unsigned td,
+                      hipStream_t st, const FusedOut &fo);
+
+// ---- hit lists in ctx->scratch, and the head of a call (score_plan.hip) ------------------------------------------
+// [counters: kHitListHead bytes][the caller's tables, up to head_bytes][HitRecord x cap][Candidate x ccap][tail]
+// (the counters get 256 bytes of their own: the scans' atomics on them would otherwise fight with every read of a job
+// table entry in the same cache line -- measured +30 % on the re-scoring kernel at 10^6 hits)
+constexpr size_t kHitListHead = 256;
+// reserves the block and points fo's counters and lists into it; the tail starts behind the last candidate
+int reserve_hit_lists(lm_hip_ctx *ctx, size_t head_bytes, unsigned long long cap, unsigned long long ccap, size_t tail_bytes,
+                      FusedOut *fo, char **base);
+// The first `head_bytes` of the block: `zero_bytes` of zeros, then the parts.  A head of at most half the pinned block is
+// assembled in its upper half and reaches the device as ONE copy (memsets and staged copies from pageable memory cost more
+// than a sample pass); a larger one takes a memset of the counters and a copy (src) or 32-bit fill (no src) per part.
+struct HeadPart { size_t off; const void *src; size_t bytes; unsigned fill; };
+int upload_head(lm_hip_ctx *ctx, hipStream_t st, char *base, size_t head_bytes, size_t zero_bytes, const HeadPart *parts, size_t nparts);
 
 // ---- fused reductions of sliced motifs (M > kMaxFastM at C = 32) -----------------------------------
 //

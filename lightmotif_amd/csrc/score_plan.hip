@@ -1,4 +1,4 @@
-// score_plan.hip -- registry of the unrolled kernels and the stream geometry every launch shares (score_launch.hpp).
+// score_plan.hip -- kernel registry, the stream geometry every launch shares, scan planner and launcher of the fused routes.
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -7,32 +7,7 @@
 
 namespace lm {
 
-// ---- registry of the unrolled C=32 kernels ---------------------------------------
-
-void register_score_c32_0(const KernelRegistry &r);
-void register_score_c32_1(const KernelRegistry &r);
-void register_score_c32_2(const KernelRegistry &r);
-void register_score_c32_3(const KernelRegistry &r);
-void register_score_c32_4(const KernelRegistry &r);
-void register_score_c32_5(const KernelRegistry &r);
-void register_score_c32_6(const KernelRegistry &r);
-void register_score_c32_7(const KernelRegistry &r);
-void register_score_c32_8(const KernelRegistry &r);
-void register_score_c32_long_40(const KernelRegistry &r);
-void register_score_c32_long_44(const KernelRegistry &r);
-void register_score_c32_long_48(const KernelRegistry &r);
-void register_score_c32_long_52(const KernelRegistry &r);
-void register_score_c32_long_56(const KernelRegistry &r);
-void register_score_c32_long_60(const KernelRegistry &r);
-void register_score_c32_long_64(const KernelRegistry &r);
-void register_score_pair_65(const KernelRegistry &r);
-void register_score_pair_81(const KernelRegistry &r);
-void register_score_c32_xlong_72(const KernelRegistry &r);
-void register_score_c32_xlong_80(const KernelRegistry &r);
-void register_score_c32_xlong_88(const KernelRegistry &r);
-
-void register_score_pair_97(const KernelRegistry &r);
-void register_score_pair_113(const KernelRegistry &r);
+// ---- registry of the unrolled kernels (score_registry.hpp) ------------------------------------------------
 
 static ScoreC32Launcher g_c32[kMaxStoreM + 1][kRegistrySlots];  // rows kMaxFastM + 1 ..: the long family (M % 4 == 0); beyond kMaxLongM: store only (M % 8 == 0)
 static ScoreC32Launcher g_c32w[kMaxStoreM + 1][kRegistrySlots];  // wide alphabets (lds_wide(K))
@@ -46,45 +21,52 @@ static ScoreU8Launcher g_u8[kMaxFastM + 1];
 static ScoreU8Launcher g_u8_pairs[kMaxFastM + 1];
 static PrefilterMultiLauncher g_pre2_multi[kMaxFastM + 1];
 static char g_c32_names[kMaxStoreM + 1][3][32];
+static char g_hole[96];  // "" = every promised row is filled
 static std::once_flag g_c32_once;
+
+// what LM_REGISTERING_UNITS promises: the store kernel for every M up to kMaxFastM and the padded lengths of the long
+// (M % 4 == 0) and very long (M % 8 == 0) families; the DNA pair scan from 2 to kMaxPairM; one-symbol scan and u8 kernels
+static void find_hole()
+{
+    auto check = [](bool filled, const char *row, int m) {
+        if (!filled && !g_hole[0])
+            snprintf(g_hole, sizeof g_hole, "kernel registry: no %s kernel for M = %d (a unit of the build is not registered)", row, m);
+    };
+    for (int m = 1; m <= kMaxStoreM; ++m)
+        if (m <= kMaxFastM || (m <= kMaxLongM ? m % 4 == 0 : m % 8 == 0))
+            check(g_c32[m][SLOT_STORE] && g_c32w[m][SLOT_STORE], "store", m);
+    for (int m = 2; m <= kMaxPairM; ++m)
+        check(g_pre2[m], "pair scan", m);
+    for (int m = 1; m <= kMaxFastM; ++m)
+        check(g_pre[m] && g_prew[m] && g_u8[m] && g_u8w[m], "one-symbol scan or u8", m);
+}
 
 static void init_registry()
 {
     const KernelRegistry r{g_c32, g_pre, g_pre2, g_pre2_protein, g_u8, g_u8_pairs, g_pre2_multi, g_c32w, g_prew, g_u8w, g_preblk};
-    register_score_c32_0(r);
-    register_score_c32_1(r);
-    register_score_c32_2(r);
-    register_score_c32_3(r);
-    register_score_c32_4(r);
-    register_score_c32_5(r);
-    register_score_c32_6(r);
-    register_score_c32_7(r);
-    register_score_c32_8(r);
-    register_score_c32_long_40(r);
-    register_score_c32_long_44(r);
-    register_score_c32_long_48(r);
-    register_score_c32_long_52(r);
-    register_score_c32_long_56(r);
-    register_score_c32_long_60(r);
-    register_score_c32_long_64(r);
-    register_score_c32_xlong_72(r);
-    register_score_c32_xlong_80(r);
-    register_score_c32_xlong_88(r);
-    register_score_pair_65(r);
-    register_score_pair_81(r);
-    register_score_pair_97(r);
-    register_score_pair_113(r);
+#define LM_CALL_UNIT(f) f(r);
+    LM_REGISTERING_UNITS(LM_CALL_UNIT)
+#undef LM_CALL_UNIT
+    find_hole();
     for (int m = 0; m <= kMaxStoreM; ++m)
         for (int mode = 0; mode < 3; ++mode)
             snprintf(g_c32_names[m][mode], sizeof g_c32_names[m][mode], "score_c32<%d,%d>", m, mode);
 }
 
-ScoreC32Launcher score_c32_lookup(int M, int mode, bool wide)
+const char *score_registry_hole()
 {
     std::call_once(g_c32_once, init_registry);
-    if (M < 1 || M > kMaxStoreM || mode < 0 || mode > 2)
+    return g_hole[0] ? g_hole : nullptr;
+}
+
+ScoreC32Launcher score_c32_lookup(int M, int slot, bool wide)
+{
+    std::call_once(g_c32_once, init_registry);
+    if (M < 1 || M > kMaxStoreM || slot < 0 || slot >= kRegistrySlots)
         return nullptr;
-    return (wide ? g_c32w : g_c32)[M][mode];
+    if (slot == SLOT_STORE_C16 && M > kMaxFastM)
+        return nullptr;  // the C = 16 kernel is a member of the short family only
+    return (wide ? g_c32w : g_c32)[M][slot];
 }
 
 PrefilterLauncher score_c32_prefilter_lookup(int M, bool wide, bool blocks)
@@ -106,18 +88,6 @@ PrefilterMultiLauncher score_c32_prefilter2_multi_lookup(int M)
     std::call_once(g_c32_once, init_registry);
     return (M >= 1 && M <= kMaxFastM) ? g_pre2_multi[M] : nullptr;
 }
-
-static ScoreC32Launcher c32_slot(int M, int slot, bool wide)
-{
-    std::call_once(g_c32_once, init_registry);
-    return (M >= 1 && M <= kMaxStoreM) ? (wide ? g_c32w : g_c32)[M][slot] : nullptr;
-}
-
-ScoreC32Launcher score_c32_lookup_store_argmax(int M, bool wide) { return c32_slot(M, 8, wide); }
-ScoreC32Launcher score_c32_lookup_continue(int M, bool wide) { return c32_slot(M, 9, wide); }
-ScoreC32Launcher score_c32_lookup_c16(int M, bool wide) { return c32_slot(M <= kMaxFastM ? M : 0, 10, wide); }
-ScoreC32Launcher score_c32_lookup_store_track(int M, bool wide) { return c32_slot(M, 11, wide); }
-ScoreC32Launcher score_c32_lookup_ql(int M, bool wide) { return c32_slot(M, 7, wide); }
 
 ScoreU8Launcher score_c32_lookup_u8(int M, bool pairs, bool wide)
 {
@@ -234,8 +204,10 @@ size_t generic_lds(const lm_hip_pssm *p, int *use_lds)
 
 // ---- batches ---------------------------------------------------------------------------
 
-int batch_fork(lm_hip_ctx *ctx)
+int BatchStreams::fork()
 {
+    if (!two)
+        return LM_HIP_OK;
     if (!ctx->aux_stream) {
         LM_HIP_TRY(hipStreamCreateWithFlags(&ctx->aux_stream, hipStreamNonBlocking));
         LM_HIP_TRY(hipEventCreateWithFlags(&ctx->fork_event, hipEventDisableTiming));
@@ -246,10 +218,148 @@ int batch_fork(lm_hip_ctx *ctx)
     return LM_HIP_OK;
 }
 
-int batch_join(lm_hip_ctx *ctx)
+int BatchStreams::join()
 {
+    if (!two)
+        return LM_HIP_OK;
     LM_HIP_TRY(hipEventRecord(ctx->join_event, ctx->aux_stream));
     LM_HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->join_event, 0));
+    return LM_HIP_OK;
+}
+
+// ---- the scans of a batch, hit lists and the head of a call (score_launch.hpp) -------------------------------
+
+ScanPlan plan_scans(const lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n, const std::vector<JobGroup> &groups, bool allow_drop)
+{
+    ScanPlan sp;
+    sp.groups.resize(groups.size());
+    sp.order.reserve(n + 4 * groups.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const JobGroup &g = groups[gi];
+        ScanGroup &sg = sp.groups[gi];
+        sg.pos = sp.order.size();
+        const lm_hip_pssm *p0 = jobs[g.idx[0]].pssm;
+        sg.multi = g.kind == KIND_PREFILTER2 && ctx->multi_motif && g.idx.size() >= 2 && p0->k == 5 &&
+                   score_c32_prefilter2_multi_lookup((int)p0->m);
+        for (size_t i : g.idx) {
+            sg.multi = sg.multi && jobs[i].pssm->d_image2_multi != nullptr;
+            sp.order.push_back(ScanPlan::Pos{i, false});
+        }
+        if (sg.multi) {
+            sg.per_pass = prefilter2_multi((int)p0->m);
+            while ((sp.order.size() - sg.pos) % sg.per_pass)
+                sp.order.push_back(ScanPlan::Pos{g.idx.back(), true});
+        }
+    }
+    const lm_hip_pssm *p = jobs[0].pssm;
+    if (allow_drop && n == 1 && groups.size() == 1 && groups[0].kind == KIND_PREFILTER2 && ctx->drop_last && p->d_image2_drop &&
+        score_c32_prefilter2_lookup((int)p->m - 1, (int)p->k))
+        sp.drop = plan_c32(ctx, MotifShape{p->m - 1, p->k, true}, jobs[0], false, 2, 1);
+    return sp;
+}
+
+const void *scan_table(const ScanPlan &sp, size_t gi, int kind, const ScoreArgs &a)
+{
+    const lm_hip_pssm *p = a.pssm;
+    return sp.drop.ok                ? (const void *)p->d_image2_drop
+           : sp.groups[gi].multi     ? (const void *)p->d_image2_multi
+           : kind == KIND_PREFILTER2 ? (const void *)p->d_image2
+           : kind == KIND_PREFILTER  ? (const void *)p->d_image
+           : kind == KIND_EXACT      ? (const void *)exact_motif(p, a.d_seq).table
+                                     : (const void *)p->d_table;
+}
+
+void record_scan_shape(lm_hip_ctx *ctx, const ScanPlan &sp, const std::vector<JobGroup> &groups, const ScoreArgs *jobs, size_t n)
+{
+    ctx->last_scan_rows = ctx->last_scan_lds_bytes = 0;
+    if (n != 1 || groups.size() != 1)
+        return;
+    const size_t scanned = jobs[0].pssm->m - (sp.drop.ok ? 1 : 0);
+    const size_t em = groups[0].kind == KIND_EXACT ? exact_motif(jobs[0].pssm, jobs[0].d_seq).m : scanned;
+    ctx->last_scan_lds_bytes = scan_lds_bytes(groups[0].kind, em, jobs[0].pssm->k);
+    ctx->last_scan_rows = ctx->last_scan_lds_bytes ? (unsigned)scanned : 0u;
+}
+
+int launch_prefilter_scan(lm_hip_ctx *ctx, int kind, size_t m, size_t k, bool blocks, const C32Plan &plan, hipStream_t st,
+                          const uint8_t *d_seq, size_t row_begin, size_t row_end, const unsigned *image, unsigned td,
+                          const FusedOut &fo)
+{
+    const bool pairs = kind == KIND_PREFILTER2;
+    ctx->last_kernel = pairs ? "score_c32_prefilter2" : blocks ? "score_c32_prefilter_blk" : "score_c32_prefilter";
+    PrefilterLauncher fn = pairs ? score_c32_prefilter2_lookup((int)m, (int)k) : score_c32_prefilter_lookup((int)m, lds_wide((int)k), blocks);
+    if (!fn)
+        return fail(LM_HIP_ERR_HIP, "no %s kernel for M = %zu, K = %zu", ctx->last_kernel, m, k);
+    LM_HIP_TRY(fn(plan.grid, plan.lds, st, d_seq, image, (int)k, row_begin, row_end, plan.T, plan.nstreams, td, fo));
+    return LM_HIP_OK;
+}
+
+int launch_group_scan(lm_hip_ctx *ctx, const ScanPlan &sp, size_t gi, const JobGroup &g, const ScoreArgs &a, int mode, unsigned td,
+                      hipStream_t st, const FusedOut &fo)
+{
+    const lm_hip_pssm *p = a.pssm;
+    const ScanGroup &sg = sp.groups[gi];
+    if (sg.multi) {  // several motifs of this length per pass over the sequence
+        dim3 grid = g.plan.grid;
+        grid.y = (unsigned)((g.idx.size() + sg.per_pass - 1) / sg.per_pass);
+        ctx->last_kernel = "score_c32_prefilter2_multi";
+        LM_HIP_TRY(score_c32_prefilter2_multi_lookup((int)p->m)(grid, st, a.d_seq, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, fo));
+        return LM_HIP_OK;
+    }
+    if (g.kind == KIND_PREFILTER2 && sp.drop.ok)
+        return launch_prefilter_scan(ctx, g.kind, p->m - 1, p->k, false, sp.drop, st, a.d_seq, a.row_begin, a.row_end,
+                                     p->d_image2_drop, td, fo);
+    if (g.kind == KIND_PREFILTER || g.kind == KIND_PREFILTER2)
+        return launch_prefilter_scan(ctx, g.kind, p->m, p->k, block_scan(ctx, a), g.plan, st, a.d_seq, a.row_begin, a.row_end,
+                                     g.kind == KIND_PREFILTER2 ? p->d_image2 : p->d_image, td, fo);
+    if (g.kind != KIND_EXACT || (mode != MODE_ARGMAX && mode != MODE_THRESHOLD))  // (a mode is a registry slot only up to MODE_THRESHOLD)
+        return fail(LM_HIP_ERR_BAD_ARGS, "launch_group_scan: no fused kernel for kind %d in mode %d", g.kind, mode);
+    const ExactMotif em = exact_motif(p, a.d_seq);  // (a group shares length, hence padding)
+    FusedOut efo = fo;
+    efo.lead_rows = em.lead;
+    ScoreC32Launcher fn = score_c32_lookup((int)em.m, mode, lds_wide((int)p->k));
+    ctx->last_kernel = score_c32_name((int)em.m, mode);
+    if (!fn)
+        return fail(LM_HIP_ERR_HIP, "no %s kernel", ctx->last_kernel);
+    LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, st, a.d_seq, em.table, (int)p->k, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams,
+                  nullptr, efo));
+    return LM_HIP_OK;
+}
+
+int reserve_hit_lists(lm_hip_ctx *ctx, size_t head_bytes, unsigned long long cap, unsigned long long ccap, size_t tail_bytes,
+                      FusedOut *fo, char **base)
+{
+    const size_t off_cands = head_bytes + cap * sizeof(HitRecord);
+    LM_TRY(ctx->scratch.reserve(off_cands + ccap * sizeof(Candidate) + tail_bytes));
+    char *b = static_cast<char *>(ctx->scratch.ptr);
+    fo->hit_count = reinterpret_cast<unsigned long long *>(b);
+    fo->cand_count = fo->hit_count + 1;
+    fo->hits = reinterpret_cast<HitRecord *>(b + head_bytes);
+    fo->hit_capacity = cap;
+    fo->cands = reinterpret_cast<Candidate *>(b + off_cands);
+    fo->cand_capacity = ccap;
+    *base = b;
+    return LM_HIP_OK;
+}
+
+int upload_head(lm_hip_ctx *ctx, hipStream_t st, char *base, size_t head_bytes, size_t zero_bytes, const HeadPart *parts, size_t nparts)
+{
+    if (head_bytes <= kPinnedBytes / 2) {
+        char *head = static_cast<char *>(ctx->pinned) + kPinnedBytes / 2;
+        memset(head, 0, zero_bytes);
+        for (size_t i = 0; i < nparts; ++i)
+            if (parts[i].src)
+                memcpy(head + parts[i].off, parts[i].src, parts[i].bytes);
+            else
+                std::fill_n(reinterpret_cast<unsigned *>(head + parts[i].off), parts[i].bytes / 4, parts[i].fill);
+        LM_HIP_TRY(hipMemcpyAsync(base, head, head_bytes, hipMemcpyHostToDevice, st));
+        return LM_HIP_OK;
+    }
+    LM_HIP_TRY(hipMemsetAsync(base, 0, 16, st));
+    for (size_t i = 0; i < nparts; ++i)
+        if (parts[i].src)
+            LM_HIP_TRY(hipMemcpyAsync(base + parts[i].off, parts[i].src, parts[i].bytes, hipMemcpyHostToDevice, st));
+        else
+            LM_HIP_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(base + parts[i].off), (int)parts[i].fill, parts[i].bytes / 4, st));
     return LM_HIP_OK;
 }
 

@@ -356,7 +356,4 @@ hipError_t score_c32_prefilter_launch(dim3 grid, size_t lds_bytes, hipStream_t s
     return hipGetLastError();
 }
 
-// `blocks`: the scan on 4-row symbol blocks (score_prefilter_blk.hpp: K = 21, 4-byte aligned matrix)
-PrefilterLauncher score_c32_prefilter_lookup(int M, bool wide = false, bool blocks = false);
-
 }  // namespace lm

@@ -837,6 +837,4 @@ hipError_t score_c32_prefilter2_launch(dim3 grid, size_t lds_bytes, hipStream_t 
     return hipGetLastError();
 }
 
-PrefilterLauncher score_c32_prefilter2_lookup(int M, int K = 5);
-
 }  // namespace lm

@@ -60,7 +60,7 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
         const size_t mp = a.pssm->m + a.pssm->lead;
         const MotifShape ms{mp, a.pssm->k, false};
         const C32Plan pp = plan_c32(ctx, ms, a, true, 0, 1, store_rows_hint(mp, a.cols), true);
-        ScoreC32Launcher pfn = a.cols == 16 ? score_c32_lookup_c16((int)mp, wide) : score_c32_lookup_ql((int)mp, wide);
+        ScoreC32Launcher pfn = a.cols == 16 ? score_c32_lookup((int)mp, SLOT_STORE_C16, wide) : score_c32_lookup((int)mp, SLOT_STORE_QL, wide);
         if (pp.ok && pfn) {
             fo.lead_rows = (unsigned)a.pssm->lead;
             ctx->last_kernel = score_c32_name((int)mp, MODE_STORE);
@@ -70,16 +70,16 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             return LM_HIP_OK;
         }
     }
-    const bool c16 = a.cols == 16 && dwords && score_c32_lookup_c16((int)a.pssm->m, wide);
+    const bool c16 = a.cols == 16 && dwords && score_c32_lookup((int)a.pssm->m, SLOT_STORE_C16, wide);
     const C32Plan p = a.pssm->m <= (size_t)kMaxFastM ? plan_c32(ctx, MotifShape{a.pssm->m, a.pssm->k, false}, a, true, 0, 1,
                                                                   store_rows_hint(a.pssm->m, a.cols), c16)
                                                       : C32Plan{};  // longer: the slices below
     if (p.ok) {
-        ScoreC32Launcher fn = score_c32_lookup((int)a.pssm->m, MODE_STORE, wide);
-        if (dwords && score_c32_lookup_ql((int)a.pssm->m, wide))
-            fn = score_c32_lookup_ql((int)a.pssm->m, wide);  // dword symbol loads (M % 4 == 0)
+        ScoreC32Launcher fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE, wide);
+        if (dwords && score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide))
+            fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide);  // dword symbol loads (M % 4 == 0)
         if (c16)
-            fn = score_c32_lookup_c16((int)a.pssm->m, wide);  // four streams of 16 columns per wavefront
+            fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE_C16, wide);  // four streams of 16 columns per wavefront
         ctx->last_kernel = score_c32_name((int)a.pssm->m, MODE_STORE);
         LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, a.pssm->d_table, (int)a.pssm->k,
                       a.row_begin, a.row_end, p.T, p.nstreams, a.d_out, fo));
@@ -106,9 +106,9 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             FusedOut pfo = fo;
             pfo.lead_rows = (unsigned)part.lead;
             if (i == 0) {
-                ScoreC32Launcher fn = score_c32_lookup_ql((int)part.m, wide);
+                ScoreC32Launcher fn = score_c32_lookup((int)part.m, SLOT_STORE_QL, wide);
                 if (!fn)
-                    fn = score_c32_lookup((int)part.m, MODE_STORE, wide);
+                    fn = score_c32_lookup((int)part.m, SLOT_STORE, wide);
                 LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, sa.d_seq, part.d_table, (int)a.pssm->k, a.row_begin, a.row_end,
                               p.T, p.nstreams, a.d_out, pfo));
                 continue;
@@ -116,7 +116,7 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             const unsigned long long nfull = n / p.T;
             if (nfull) {
                 const dim3 grid((unsigned)((nfull + kStreamsPerBlock - 1) / kStreamsPerBlock));
-                LM_HIP_TRY(score_c32_lookup_continue((int)part.m, wide)(grid, p.lds, ctx->stream, sa.d_seq, part.d_table,
+                LM_HIP_TRY(score_c32_lookup((int)part.m, SLOT_CONTINUE, wide)(grid, p.lds, ctx->stream, sa.d_seq, part.d_table,
                                                                   (int)a.pssm->k, a.row_begin, a.row_begin + nfull * p.T,
                                                                   p.T, nfull, a.d_out, pfo));
             }
@@ -407,7 +407,7 @@ int launch_score_store_argmax(lm_hip_ctx *ctx, const ScoreArgs &a, ArgmaxRecord 
     const float *pad_table = longm ? em.table : a.pssm->d_table_pad;
     const MotifShape ms{mk, a.pssm->k, false};
     const C32Plan p = mk >= 1 ? plan_c32(ctx, ms, a, true) : C32Plan{};
-    ScoreC32Launcher fn = p.ok ? score_c32_lookup_store_argmax((int)mk, lds_wide((int)a.pssm->k)) : nullptr;
+    ScoreC32Launcher fn = p.ok ? score_c32_lookup((int)mk, SLOT_STORE_ARGMAX, lds_wide((int)a.pssm->k)) : nullptr;
     if (!fn || reinterpret_cast<uintptr_t>(a.d_seq) % 4 != 0)
         return launch_score_store(ctx, a);
     if (a.out_stride != 32)
@@ -513,7 +513,7 @@ int launch_score_store_track(lm_hip_ctx *ctx, const ScoreArgs &a, ArgmaxRecord *
                        reinterpret_cast<uintptr_t>(a.d_seq) % 4 == 0)
                           ? plan_c32(ctx, MotifShape{mk, a.pssm->k, false}, a, true, 0, 1, store_rows_hint(mk, a.cols))
                           : C32Plan{};
-    ScoreC32Launcher fn = p.ok ? score_c32_lookup_store_track((int)mk, lds_wide((int)a.pssm->k)) : nullptr;
+    ScoreC32Launcher fn = p.ok ? score_c32_lookup((int)mk, SLOT_STORE_TRACK, lds_wide((int)a.pssm->k)) : nullptr;
     auto ensure_records = [&](size_t need) {  // (re)allocate the pinned record block of the handle
         if (!host_fold || need <= host_fold->h_records_cap)
             return;

@@ -208,6 +208,112 @@ int launch_rescore(lm_hip_ctx *ctx, hipStream_t st, const RescoreJob *d_jobs, co
     return LM_HIP_OK;
 }
 
+// the scans of one attempt, alternating between the two streams; `fo` keeps what the last group set
+static int launch_threshold_scans(lm_hip_ctx *ctx, const ScoreArgs *jobs, const float *ts, const unsigned *tds, size_t n,
+                                  const std::vector<JobGroup> &groups, const ScanPlan &sp, const BatchParams *d_bparams,
+                                  FusedOut &fo, bool *any_candidates)
+{
+    BatchStreams streams(ctx, groups.size());
+    scan_timer_begin(ctx, ctx->stream);
+    LM_TRY(streams.fork());
+    for (size_t gi = 0; gi < groups.size(); ++gi) {
+        const JobGroup &g = groups[gi];
+        const size_t i = g.idx[0];
+        const ScoreArgs &a = jobs[i];
+        // (launch order and stream balance do not matter: most expensive length class first on the less loaded stream
+        //  measured 14.59 against 14.61 ms of scans on the JASPAR batch, round 6 -- the scans are LDS-bound, not gap-bound)
+        hipStream_t st = streams.next();
+        fo.threshold = ts[i];
+        fo.job_key = (unsigned long long)i << 40;
+        fo.batch = (n > 1 && !kind_solo(g.kind)) ? d_bparams + sp.groups[gi].pos : nullptr;
+        if (!kind_solo(g.kind)) {
+            // (the drop-last form scans M - 1 rows: what the last row may add comes off the threshold)
+            LM_TRY(launch_group_scan(ctx, sp, gi, g, a, MODE_THRESHOLD, sp.drop.ok ? tds[i] - a.pssm->drop_dmax : tds[i], st, fo));
+            *any_candidates = true;
+        } else if (g.kind == KIND_CHUNKED) {  // appends hits directly, chunk by chunk, on ctx->stream
+            const FusedOut cfo = fo;
+            LM_TRY(for_each_scored_chunk(ctx, a, [&](const float *buf, unsigned long long c0, unsigned long long rows) {
+                const unsigned long long ncells = rows * a.cols;
+                const unsigned grid = (unsigned)std::max<unsigned long long>(
+                    std::min<unsigned long long>((ncells / 4 + kBlock - 1) / kBlock, (unsigned long long)ctx->num_cus * 16), 1);
+                hipLaunchKernelGGL(chunk_emit_hits, dim3(grid), dim3(kBlock), 0, ctx->stream, buf, ncells, c0,
+                                   (unsigned)a.cols, cfo);
+                LM_HIP_TRY(hipGetLastError());
+                return (int)LM_HIP_OK;
+            }));
+        } else {
+            ctx->last_kernel = "score_generic<2>";  // appends hits directly
+            LM_TRY(launch_generic<MODE_THRESHOLD>(ctx, a, fo, generic_grid(ctx, (unsigned long long)(a.row_end - a.row_begin) * a.cols), st));
+        }
+    }
+    LM_TRY(streams.join());
+    scan_timer_end(ctx, ctx->stream);
+    return LM_HIP_OK;
+}
+
+// the two lists of an attempt: capacities in, counts out
+struct ListSizes {
+    unsigned long long cap, ccap, count, ncand;
+    bool ordered;  // the speculative ordering held: one synchronisation
+};
+
+// the tail of an attempt: counts and ordered list; *again: a list overflowed, its capacity in `ls` has grown: scan again
+static int order_or_grow(lm_hip_ctx *ctx, bool speculate, const FusedOut &fo, const char *base, const ShortOrder &so,
+                         const SegmentCut *segp, unsigned long long expected, size_t n, unsigned long long max_low, int emit,
+                         size_t cols, HitOutput *out, ListSizes *ls, bool *again)
+{
+    unsigned long long &cap = ls->cap, &ccap = ls->ccap, &count = ls->count, &ncand = ls->ncand;
+    *again = true;
+    if (speculate) {
+        // First try: enqueue the ordering right behind the scans, sized from the previous
+        // call's count, and learn the counts from the same single synchronisation.
+        int status = 0;
+        unsigned long long counts[2] = {0, 0};
+        LM_TRY(order_hits(ctx, fo.hits, fo.hit_count, ~0ull, cap, ccap, expected, n, max_low, emit, cols, out,
+                          &status, counts, &so, segp));
+        count = counts[0];
+        ncand = counts[1];
+        ls->ordered = status == 0;
+        if (status == 1) {  // a list overflowed: grow and run the scans again
+            ctx->last_cand_count = ncand;
+            if (ncand > ccap) {
+                ccap = ncand + ncand / 8 + 64;
+                return LM_HIP_OK;
+            }
+            ctx->last_hit_count = count;
+            cap = count + count / 8 + 64;
+            return LM_HIP_OK;
+        }
+    } else {
+        LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, base, 16, hipMemcpyDeviceToHost, ctx->stream));
+        LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        count = static_cast<unsigned long long *>(ctx->pinned)[0];
+        ncand = static_cast<unsigned long long *>(ctx->pinned)[1];
+        if (ncand > ccap) {
+            // the hit count of a truncated candidate list means nothing yet
+            ctx->last_cand_count = ncand;
+            ccap = ncand + ncand / 8 + 64;
+            return LM_HIP_OK;
+        }
+        if (count > cap) {
+            ctx->last_hit_count = count;
+            cap = count + count / 8 + 64;
+            return LM_HIP_OK;
+        }
+    }
+    *again = false;
+    ctx->last_cand_count = ncand;
+    ctx->last_hit_count = count;
+    if (!ls->ordered) {  // exact form: the count is known
+        int status = 0;
+        unsigned long long counts[2];
+        // (after a short form that gave up, the list's counters have been cleared: their copy still holds them)
+        LM_TRY(order_hits(ctx, fo.hits, so.on ? so.counters_copy : fo.hit_count, count, cap, ccap, count, n, max_low, emit, cols,
+                          out, &status, counts, nullptr, segp));
+    }
+    return LM_HIP_OK;
+}
+
 // Fused score+threshold of `n` jobs.  The C = 32 kernels flag candidate row ranges
 // (discrete prefilter or exact f32 compare), `rescore_candidates` turns them into
 // (key, score) hit records, key = (job << 40) | row-major cell index or sequence
@@ -241,10 +347,11 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
     // default p-value is 1e-5, main.rs:487), at least what the previous call on this
     // context needed, never more than every cell; twice that many candidate pieces.
     // An overflow of either list re-runs the batch with the exact counts.
-    unsigned long long cap = std::max<unsigned long long>(total_cells / 8192, 1 << 16);
-    cap = std::max(cap, ctx->last_hit_count + ctx->last_hit_count / 2);
-    cap = std::min(cap, total_cells + 64);
-    unsigned long long ccap = std::max(2 * cap, ctx->last_cand_count + ctx->last_cand_count / 2);
+    ListSizes ls{};
+    ls.cap = std::max<unsigned long long>(total_cells / 8192, 1 << 16);
+    ls.cap = std::max(ls.cap, ctx->last_hit_count + ctx->last_hit_count / 2);
+    ls.cap = std::min(ls.cap, total_cells + 64);
+    ls.ccap = std::max(2 * ls.cap, ctx->last_cand_count + ctx->last_cand_count / 2);
     std::vector<RescoreJob> rjobs(n);
     const auto t_begin = std::chrono::steady_clock::now();
     // which kernel scores each job: the discrete prefilter (score_prefilter.hpp) when a
@@ -271,84 +378,35 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         }
         return plan_c32(ctx, a, false).ok ? (int)KIND_EXACT : chunked_ok(ctx, a) ? (int)KIND_CHUNKED : (int)KIND_GENERIC;
     });
+    const ScanPlan sp = plan_scans(ctx, jobs, n, groups, (unsigned long long)jobs[0].pssm->drop_dmax * 4 <= tds[0]);
+    record_scan_shape(ctx, sp, groups, jobs, n);
     const unsigned long long key_rows =
         keys == HitKeys::Position ? (unsigned long long)(jobs[0].row_end - jobs[0].row_begin) : 0;
-    // job table in launch order: the jobs of a group are contiguous from group_pos[g] on.  Groups
-    // of the pair scan with several jobs run `per_pass[g]` motifs per pass
-    // (score_c32_prefilter2_multi) and are padded to a multiple of that with entries that flag nothing.
+    // job table in launch order; a padding position copies its group's last entry and flags nothing (no sum reaches 2^32 - 1)
     std::vector<BatchParams> bparams;
-    std::vector<size_t> group_pos(groups.size());
-    std::vector<int> per_pass(groups.size(), 1);
-    bparams.reserve(n + 4 * groups.size());
-    for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const JobGroup &g = groups[gi];
-        group_pos[gi] = bparams.size();
-        // several motifs per pass (score_c32_prefilter2_multi): every matrix of the group needs its table in that kernel's layout
-        bool multi = g.kind == KIND_PREFILTER2 && ctx->multi_motif && n > 1 && g.idx.size() >= 2 && jobs[g.idx[0]].pssm->k == 5 &&
-                     score_c32_prefilter2_multi_lookup((int)jobs[g.idx[0]].pssm->m);
-        for (size_t i : g.idx)
-            multi = multi && jobs[i].pssm->d_image2_multi != nullptr;
-        for (size_t i : g.idx) {
+    bparams.reserve(sp.order.size());
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+        for (size_t pos = sp.groups[gi].pos; pos < sp.group_end(gi); ++pos) {
+            const size_t i = sp.order[pos].job;
             const ScoreArgs &a = jobs[i];
             if (keys == HitKeys::Position && a.row_end - a.row_begin != key_rows)
                 return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: position keys need equal row ranges");
-            bparams.push_back(BatchParams{multi                      ? (const void *)a.pssm->d_image2_multi
-                                          : g.kind == KIND_PREFILTER2 ? (const void *)a.pssm->d_image2
-                                          : g.kind == KIND_PREFILTER ? (const void *)a.pssm->d_image
-                                          : g.kind == KIND_EXACT     ? (const void *)exact_motif(a.pssm, a.d_seq).table
-                                                                     : (const void *)a.pssm->d_table,
-                                          nullptr, ts[i], tds[i], (unsigned long long)i << 40});
+            bparams.push_back(BatchParams{scan_table(sp, gi, groups[gi].kind, a), nullptr, ts[i],
+                                          sp.order[pos].pad ? 0xffffffffu : tds[i], (unsigned long long)i << 40});
             rjobs[i] = RescoreJob{a.d_seq + a.row_begin * a.seq_stride, a.pssm->d_dense,
                                   (unsigned)a.pssm->m, (unsigned)a.pssm->k, ts[i], 0, key_rows};
         }
-        const int m = (int)jobs[g.idx[0]].pssm->m;
-        if (multi) {
-            per_pass[gi] = prefilter2_multi(m);
-            while ((bparams.size() - group_pos[gi]) % per_pass[gi]) {
-                BatchParams pad = bparams.back();
-                pad.td = 0xffffffffu;  // no sum reaches it: the padding job flags nothing
-                bparams.push_back(pad);
-            }
-        }
-    }
     const size_t nbp = bparams.size();
-    // One pair scan of a motif of M = 20, 24, ... 36 rows: its first M - 1 rows are looked up and the last row is credited with
-    // its best weight (lm_hip_pssm::d_image2_drop) -- table rows of one 16-byte read less, up to four times the candidate
-    // pieces, identical hits (every candidate is re-scored over all M rows).  Not when the last row carries a large part of
-    // the threshold: the scan would flag too much.
-    C32Plan drop_plan;
-    if (n == 1 && groups.size() == 1 && groups[0].kind == KIND_PREFILTER2 && ctx->drop_last && jobs[0].pssm->d_image2_drop &&
-        (unsigned long long)jobs[0].pssm->drop_dmax * 4 <= tds[0] &&
-        score_c32_prefilter2_lookup((int)jobs[0].pssm->m - 1, (int)jobs[0].pssm->k))
-        drop_plan = plan_c32(ctx, MotifShape{jobs[0].pssm->m - 1, jobs[0].pssm->k, true}, jobs[0], false, 2, 1);
-    const bool drop_last_form = drop_plan.ok;
-    ctx->last_scan_rows = ctx->last_scan_lds_bytes = 0;
-    if (n == 1 && groups.size() == 1) {
-        const size_t scanned = jobs[0].pssm->m - (drop_last_form ? 1 : 0);
-        const size_t em = groups[0].kind == KIND_EXACT ? exact_motif(jobs[0].pssm, jobs[0].d_seq).m : scanned;
-        ctx->last_scan_lds_bytes = scan_lds_bytes(groups[0].kind, em, jobs[0].pssm->k);
-        ctx->last_scan_rows = ctx->last_scan_lds_bytes ? (unsigned)scanned : 0u;
-    }
+    const bool one_scan = n == 1 && groups.size() == 1 &&
+                          (groups[0].kind == KIND_PREFILTER || groups[0].kind == KIND_PREFILTER2 || groups[0].kind == KIND_EXACT);
     for (int attempt = 0; attempt < 3; ++attempt) {
-        // layout: [hit count u64][candidate count u64][jobs][batch][HitRecord x cap][Candidate x ccap];
-        // the head -- zeroed counters and the two job tables -- is assembled in the upper half of the
-        // pinned buffer and reaches the device as ONE copy
-        // (the counters get 256 bytes of their own: the scans' atomics on them would otherwise
-        // fight with every read of a job table entry in the same cache line -- measured +30 % on the
-        // re-scoring kernel at 10^6 hits)
-        const size_t off_jobs = 256;
+        // head of the scratch block: [counters][jobs][batch]; the batch table is only read (and sent) for several jobs
+        const size_t off_jobs = kHitListHead;
         const size_t off_batch = off_jobs + (n * sizeof(RescoreJob) + 15) / 16 * 16;
         const size_t off_hits = off_batch + (nbp * sizeof(BatchParams) + 15) / 16 * 16;
-        const size_t off_cands = off_hits + cap * sizeof(HitRecord);
-        LM_TRY(ctx->scratch.reserve(off_cands + ccap * sizeof(Candidate)));
-        char *base = static_cast<char *>(ctx->scratch.ptr);
         FusedOut fo{};
-        fo.hit_count = reinterpret_cast<unsigned long long *>(base);
-        fo.cand_count = fo.hit_count + 1;
-        fo.hits = reinterpret_cast<HitRecord *>(base + off_hits);
-        fo.hit_capacity = cap;
-        fo.cands = reinterpret_cast<Candidate *>(base + off_cands);
-        fo.cand_capacity = ccap;
+        char *base = nullptr;
+        LM_TRY(reserve_hit_lists(ctx, off_hits, ls.cap, ls.ccap, 0, &fo, &base));
         fo.key_rows = key_rows;
         RescoreJob *d_jobs = reinterpret_cast<RescoreJob *>(base + off_jobs);
         BatchParams *d_bparams = reinterpret_cast<BatchParams *>(base + off_batch);
@@ -357,156 +415,35 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         ShortOrder so;
         const unsigned long long expected = ctx->last_hit_count + ctx->last_hit_count / 4;
         // (not for a sequence set: the segment pass reads the job table and sits behind the long ordering)
-        if (attempt == 0 && !cut && ctx->speculate_order && ctx->short_order && n == 1 && groups.size() == 1 &&
-            (groups[0].kind == KIND_PREFILTER || groups[0].kind == KIND_PREFILTER2 || groups[0].kind == KIND_EXACT))
+        if (attempt == 0 && !cut && ctx->speculate_order && ctx->short_order && one_scan)
             LM_TRY(short_order_begin(ctx, expected, n, max_low, &so));
         if (so.on) {
             fo.hit_count = so.counters;
             fo.cand_count = so.counters + 1;
-        } else if (off_hits <= kPinnedBytes / 2) {
-            char *head = static_cast<char *>(ctx->pinned) + kPinnedBytes / 2;
-            memset(head, 0, off_jobs);
-            memcpy(head + off_jobs, rjobs.data(), n * sizeof(RescoreJob));
-            if (n > 1)
-                memcpy(head + off_batch, bparams.data(), nbp * sizeof(BatchParams));
-            LM_HIP_TRY(hipMemcpyAsync(base, head, n > 1 ? off_hits : off_batch, hipMemcpyHostToDevice, ctx->stream));
         } else {
-            LM_HIP_TRY(hipMemsetAsync(base, 0, 16, ctx->stream));
-            LM_HIP_TRY(hipMemcpyAsync(d_jobs, rjobs.data(), n * sizeof(RescoreJob), hipMemcpyHostToDevice,
-                                      ctx->stream));
-            LM_HIP_TRY(hipMemcpyAsync(d_bparams, bparams.data(), nbp * sizeof(BatchParams), hipMemcpyHostToDevice,
-                                      ctx->stream));
+            const HeadPart parts[2] = {{off_jobs, rjobs.data(), n * sizeof(RescoreJob), 0u},
+                                       {off_batch, bparams.data(), nbp * sizeof(BatchParams), 0u}};
+            LM_TRY(upload_head(ctx, ctx->stream, base, n > 1 ? off_hits : off_batch, kHitListHead, parts, n > 1 ? 2 : 1));
         }
-        const bool two_streams = groups.size() > 1;
-        scan_timer_begin(ctx, ctx->stream);
-        if (two_streams)
-            LM_TRY(batch_fork(ctx));
         bool any_candidates = false;
-        size_t launch = 0;
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const JobGroup &g = groups[gi];
-            const size_t bp_pos = group_pos[gi];
-            const size_t i = g.idx[0];
-            const ScoreArgs &a = jobs[i];
-            // (launch order and stream balance do not matter: most expensive length class first on the less loaded stream
-            //  measured 14.59 against 14.61 ms of scans on the JASPAR batch, round 6 -- the scans are LDS-bound, not gap-bound)
-            hipStream_t st = (two_streams && (launch++ & 1)) ? ctx->aux_stream : ctx->stream;
-            fo.threshold = ts[i];
-            fo.job_key = (unsigned long long)i << 40;
-            fo.batch = (n > 1 && !kind_solo(g.kind)) ? d_bparams + bp_pos : nullptr;
-            if (per_pass[gi] > 1) {  // several motifs of this length per pass over the sequence
-                dim3 grid = g.plan.grid;
-                grid.y = (unsigned)((g.idx.size() + per_pass[gi] - 1) / per_pass[gi]);
-                ctx->last_kernel = "score_c32_prefilter2_multi";
-                LM_HIP_TRY(score_c32_prefilter2_multi_lookup((int)a.pssm->m)(grid, st, a.d_seq, a.row_begin, a.row_end,
-                                                                            g.plan.T, g.plan.nstreams, fo));
-                any_candidates = true;
-            } else if (g.kind == KIND_PREFILTER || g.kind == KIND_PREFILTER2) {
-                const bool pairs = g.kind == KIND_PREFILTER2;
-                ctx->last_kernel = pairs ? "score_c32_prefilter2" : block_scan(ctx, a) ? "score_c32_prefilter_blk" : "score_c32_prefilter";
-                if (pairs && drop_last_form) {
-                    PrefilterLauncher fn = score_c32_prefilter2_lookup((int)a.pssm->m - 1, (int)a.pssm->k);
-                    LM_HIP_TRY(fn(drop_plan.grid, drop_plan.lds, st, a.d_seq, a.pssm->d_image2_drop, (int)a.pssm->k, a.row_begin,
-                                  a.row_end, drop_plan.T, drop_plan.nstreams, tds[i] - a.pssm->drop_dmax, fo));
-                } else {
-                    PrefilterLauncher fn = pairs ? score_c32_prefilter2_lookup((int)a.pssm->m, (int)a.pssm->k)
-                                                 : score_c32_prefilter_lookup((int)a.pssm->m, lds_wide((int)a.pssm->k), block_scan(ctx, a));
-                    LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, st, a.d_seq, pairs ? a.pssm->d_image2 : a.pssm->d_image,
-                                  (int)a.pssm->k, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, tds[i], fo));
-                }
-                any_candidates = true;
-            } else if (g.kind == KIND_EXACT) {
-                const ExactMotif em = exact_motif(a.pssm, a.d_seq);
-                FusedOut efo = fo;
-                efo.lead_rows = em.lead;
-                ScoreC32Launcher fn = score_c32_lookup((int)em.m, MODE_THRESHOLD, lds_wide((int)a.pssm->k));
-                ctx->last_kernel = score_c32_name((int)em.m, MODE_THRESHOLD);
-                LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, st, a.d_seq, em.table, (int)a.pssm->k,
-                              a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, nullptr, efo));
-                any_candidates = true;
-            } else if (g.kind == KIND_CHUNKED) {  // appends hits directly, chunk by chunk, on ctx->stream
-                const FusedOut cfo = fo;
-                LM_TRY(for_each_scored_chunk(ctx, a, [&](const float *buf, unsigned long long c0, unsigned long long rows) {
-                    const unsigned long long ncells = rows * a.cols;
-                    const unsigned grid = (unsigned)std::max<unsigned long long>(
-                        std::min<unsigned long long>((ncells / 4 + kBlock - 1) / kBlock, (unsigned long long)ctx->num_cus * 16), 1);
-                    hipLaunchKernelGGL(chunk_emit_hits, dim3(grid), dim3(kBlock), 0, ctx->stream, buf, ncells, c0,
-                                       (unsigned)a.cols, cfo);
-                    LM_HIP_TRY(hipGetLastError());
-                    return (int)LM_HIP_OK;
-                }));
-            } else {
-                ctx->last_kernel = "score_generic<2>";  // appends hits directly
-                const unsigned long long ncells =
-                    (unsigned long long)(a.row_end - a.row_begin) * a.cols;
-                LM_TRY(launch_generic<MODE_THRESHOLD>(ctx, a, fo, generic_grid(ctx, ncells), st));
-            }
-        }
-        if (two_streams)
-            LM_TRY(batch_join(ctx));
-        scan_timer_end(ctx, ctx->stream);
+        LM_TRY(launch_threshold_scans(ctx, jobs, ts, tds.data(), n, groups, sp, d_bparams, fo, &any_candidates));
         if (any_candidates || so.on) {
             LM_TRY(launch_rescore(ctx, ctx->stream, d_jobs, fo, rjobs.data(), n, &so));
             LM_HIP_TRY(hipGetLastError());
         }
         scan_timer_mark(ctx, ctx->stream, 2);
-        const int emit = keys == HitKeys::Position ? 1 : 0;
         SegmentCut seg;
         if (cut) {  // motif lengths come from the job table the re-scoring kernel reads (it moves with the scratch block)
             seg = *cut;
             seg.d_job_m = reinterpret_cast<const char *>(d_jobs) + offsetof(RescoreJob, m);
             seg.job_m_stride = sizeof(RescoreJob);
         }
-        const SegmentCut *segp = cut ? &seg : nullptr;
-        unsigned long long count = 0, ncand = 0;
         const auto t_scan = std::chrono::steady_clock::now();
-        bool ordered = false;
-        if (attempt == 0 && ctx->speculate_order) {
-            // First try: enqueue the ordering right behind the scans, sized from the previous
-            // call's count, and learn the counts from the same single synchronisation.
-            int status = 0;
-            unsigned long long counts[2] = {0, 0};
-            LM_TRY(order_hits(ctx, fo.hits, fo.hit_count, ~0ull, cap, ccap, expected, n, max_low, emit, jobs[0].cols, out,
-                              &status, counts, &so, segp));
-            count = counts[0];
-            ncand = counts[1];
-            ordered = status == 0;
-            if (status == 1) {  // a list overflowed: grow and run the scans again
-                ctx->last_cand_count = ncand;
-                if (ncand > ccap) {
-                    ccap = ncand + ncand / 8 + 64;
-                    continue;
-                }
-                ctx->last_hit_count = count;
-                cap = count + count / 8 + 64;
-                continue;
-            }
-        } else {
-            LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, base, 16, hipMemcpyDeviceToHost, ctx->stream));
-            LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-            count = static_cast<unsigned long long *>(ctx->pinned)[0];
-            ncand = static_cast<unsigned long long *>(ctx->pinned)[1];
-            if (ncand > ccap) {
-                // the hit count of a truncated candidate list means nothing yet
-                ctx->last_cand_count = ncand;
-                ccap = ncand + ncand / 8 + 64;
-                continue;
-            }
-            if (count > cap) {
-                ctx->last_hit_count = count;
-                cap = count + count / 8 + 64;
-                continue;
-            }
-        }
-        ctx->last_cand_count = ncand;
-        ctx->last_hit_count = count;
-        if (!ordered) {  // exact form: the count is known
-            int status = 0;
-            unsigned long long counts[2];
-            // (after a short form that gave up, the list's counters have been cleared: their copy still holds them)
-            LM_TRY(order_hits(ctx, fo.hits, so.on ? so.counters_copy : fo.hit_count, count, cap, ccap, count, n, max_low, emit, jobs[0].cols,
-                              out, &status, counts, nullptr, segp));
-        }
+        bool again = false;
+        LM_TRY(order_or_grow(ctx, attempt == 0 && ctx->speculate_order, fo, base, so, cut ? &seg : nullptr, expected, n, max_low,
+                             keys == HitKeys::Position ? 1 : 0, jobs[0].cols, out, &ls, &again));
+        if (again)
+            continue;
         scan_timer_read(ctx);
         if (ctx->last_phase_ms[0] >= 0)  // (time_scan) the host's share: everything of the call the events do not cover
             ctx->last_phase_ms[3] = (float)std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_begin).count() -
@@ -514,8 +451,8 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         if (getenv("LM_HIP_TRACE")) {
             const auto t_end = std::chrono::steady_clock::now();
             fprintf(stderr, "[lm_hip] fused threshold: %zu jobs, %llu candidates, %llu hits; %s; scans enqueued in "
-                            "%.3f ms, wait + ordering + read-back %.3f ms\n", n, ncand, count,
-                    ordered ? "ordered behind the scans (one synchronisation)" : "ordered after reading the count",
+                            "%.3f ms, wait + ordering + read-back %.3f ms\n", n, ls.ncand, ls.count,
+                    ls.ordered ? "ordered behind the scans (one synchronisation)" : "ordered after reading the count",
                     std::chrono::duration<double, std::milli>(t_scan - t_begin).count(),
                     std::chrono::duration<double, std::milli>(t_end - t_scan).count());
         }

@@ -194,19 +194,4 @@ hipError_t score_c32_u8_pairs_launch(dim3 grid, size_t lds_bytes, hipStream_t st
     return hipGetLastError();
 }
 
-// What a score_inst_*.hip translation unit fills in for its range of motif lengths
-// (arrays indexed by M; see score_plan.hip: init_registry).
-struct KernelRegistry {
-    ScoreC32Launcher (*c32)[kRegistrySlots];
-    PrefilterLauncher *pre, *pre2;
-    PrefilterLauncher *pre2_protein;  // the pair scan over the 441 residue pairs (K = 21)
-    ScoreU8Launcher *u8, *u8_pairs;
-    PrefilterMultiLauncher *pre2_multi;  // several motifs per pass (prefilter2_multi(M) > 1)
-    // the same kernels for alphabets of more than 16 symbols (WIDE: 8-byte LDS reads, score_kernels.hpp)
-    ScoreC32Launcher (*c32w)[kRegistrySlots];
-    PrefilterLauncher *prew;
-    ScoreU8Launcher *u8w;
-    PrefilterLauncher *preblk;  // protein one-symbol scan on 4-row symbol blocks (score_prefilter_blk.hpp)
-};
-
 }  // namespace lm

@@ -7,7 +7,7 @@
 // 4.05 ms -- two wavefronts no longer hide the gather latency of 24+ b128 reads per step), one wavefront per SIMD (262 VGPRs
 // at M' = 96, 331 at 128) is slower again (7.9 / 5.3 ... 6.9 ms), and from M' = 112 the bound of two spills by the hundred
 // (profiles/r03_xlong_ab.txt).  Compiled with the raised unroll budget of the long family (score_long_inst.hip).
-#include "score_u8.hpp"
+#include "score_registry.hpp"
 
 #ifndef LM_XLONG_M
 #error "LM_XLONG_M must be defined"
@@ -15,19 +15,16 @@
 
 namespace lm {
 
-#define LM_CAT2(a, b) a##b
-#define LM_CAT(a, b) LM_CAT2(a, b)
-
 static_assert(LM_XLONG_M > kMaxLongM && LM_XLONG_M <= kMaxStoreM && LM_XLONG_M % 8 == 0, "padded very long motif length");
 
 void LM_CAT(register_score_c32_xlong_, LM_XLONG_M)(const KernelRegistry &r)
 {
     constexpr int M = LM_XLONG_M;
     ScoreC32Launcher *tab = r.c32[M];
-    tab[MODE_STORE] = tab[7] = &score_c32_launch<M, MODE_STORE, 1>;  // dword symbol loads
+    tab[SLOT_STORE] = tab[SLOT_STORE_QL] = &score_c32_launch<M, MODE_STORE, 1>;  // dword symbol loads
     // alphabets of more than 16 symbols (8-byte LDS reads; 148 VGPRs at M' = 72, 203 at 88)
     ScoreC32Launcher *tw = r.c32w[M];
-    tw[MODE_STORE] = tw[7] = &score_c32_launch<M, MODE_STORE, 1, 32, 1>;
+    tw[SLOT_STORE] = tw[SLOT_STORE_QL] = &score_c32_launch<M, MODE_STORE, 1, 32, 1>;
 }
 
 }  // namespace lm
