@@ -439,7 +439,8 @@ int lm_hip_exchange_halo_dptr(lm_hip_ctx *ctx, lm_hip_comm *comm, uint8_t *d_sha
     const size_t nbytes = halo_rows * stride;
     const size_t rec = nbytes + 16;  // head rows + a status word (16 bytes keep the records aligned)
     const int nr = comm->nranks;
-    if ((size_t)nr * 16 > kPinnedBytes)
+    uint8_t *h_status = pinned_at<uint8_t>(ctx, kPinCommBlock, (size_t)nr * 16);
+    if (!h_status)
         return fail(LM_HIP_ERR_BAD_ARGS, "exchange_halo: too many ranks");
     LM_TRY(comm->buf.reserve(rec * ((size_t)nr + 1)));
     uint8_t *mine = static_cast<uint8_t *>(comm->buf.ptr);
@@ -453,7 +454,6 @@ int lm_hip_exchange_halo_dptr(lm_hip_ctx *ctx, lm_hip_comm *comm, uint8_t *d_sha
     LM_HIP_TRY(hipMemsetAsync(mine + nbytes, short_shard ? 1 : 0, 16, ctx->stream));
     // every rank's head rows to every rank (a few KB in total): no point-to-point pairing to get wrong
     LM_NCCL_TRY(rccl().AllGather(mine, all, rec, ncclUint8, comm->nccl, ctx->stream));
-    uint8_t *h_status = static_cast<uint8_t *>(ctx->pinned);
     LM_HIP_TRY(hipMemcpy2DAsync(h_status, 16, all + nbytes, rec, 16, (size_t)nr, hipMemcpyDeviceToHost, ctx->stream));
     LM_TRY(wait_stream(comm, ctx->stream, "exchange_halo (ncclAllGather)"));
     for (int r = 0; r < nr; ++r)
@@ -491,11 +491,11 @@ static int gather_and_combine(lm_hip_ctx *ctx, lm_hip_comm *comm, const MergeRec
                               int *found, lm_hip_coords *best, float *value)
 {
     const int n = comm->nranks;
-    if (sizeof(MergeRecord) * (size_t)n > kPinnedBytes / 2)
+    MergeRecord *h = pinned_at<MergeRecord>(ctx, kPinCommGather, (size_t)n);
+    if (!h)
         return fail(LM_HIP_ERR_BAD_ARGS, "merge: too many ranks");
     LM_TRY(order_after_side(ctx, comm));
     LM_NCCL_TRY(rccl().AllGather(d_mine, d_all, sizeof(MergeRecord), ncclUint8, comm->nccl, ctx->stream));
-    MergeRecord *h = static_cast<MergeRecord *>(ctx->pinned);
     LM_HIP_TRY(hipMemcpyAsync(h, d_all, sizeof(MergeRecord) * n, hipMemcpyDeviceToHost, ctx->stream));
     LM_TRY(wait_stream(comm, ctx->stream, "argmax merge (ncclAllGather)"));
     return combine_records(h, n, found, best, value);
@@ -519,7 +519,9 @@ int lm_hip_merge_argmax(lm_hip_ctx *ctx, lm_hip_comm *comm, int found_local, con
         mine.value = value_local;
     }
     // staged through the pinned block (the tail: gather_and_combine reads the head)
-    MergeRecord *stage = static_cast<MergeRecord *>(ctx->pinned) + comm->nranks;
+    MergeRecord *stage = pinned_at<MergeRecord>(ctx, kPinCommBlock, 1, sizeof(MergeRecord) * comm->nranks);
+    if (!stage)
+        return fail(LM_HIP_ERR_BAD_ARGS, "merge: too many ranks");
     *stage = mine;
     LM_HIP_TRY(hipMemcpyAsync(d, stage, sizeof(MergeRecord), hipMemcpyHostToDevice, ctx->stream));
     return gather_and_combine(ctx, comm, d, d + 1, found, best, value);
@@ -661,7 +663,9 @@ int lm_hip_merge_threshold(lm_hip_ctx *ctx, lm_hip_comm *comm, const lm_hip_coor
     // (1) hit counts
     LM_TRY(comm->buf.reserve(sizeof(unsigned long long) * (nr + 1)));
     unsigned long long *d_cnt = static_cast<unsigned long long *>(comm->buf.ptr);
-    unsigned long long *h = static_cast<unsigned long long *>(ctx->pinned);
+    unsigned long long *h = pinned_at<unsigned long long>(ctx, kPinCommBlock, (size_t)nr + 1);  // counts [nr], mine staged behind them
+    if (!h)
+        return fail(LM_HIP_ERR_BAD_ARGS, "merge_threshold: too many ranks");
     h[nr] = (unsigned long long)n;
     LM_HIP_TRY(hipMemcpyAsync(d_cnt + nr, h + nr, 8, hipMemcpyHostToDevice, ctx->stream));
     LM_NCCL_TRY(rccl().AllGather(d_cnt + nr, d_cnt, 8, ncclUint8, comm->nccl, ctx->stream));

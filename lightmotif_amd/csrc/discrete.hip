@@ -170,11 +170,11 @@ int launch_argmax_u8(lm_hip_ctx *ctx, const uint8_t *d_scores, size_t rows, size
     hipLaunchKernelGGL(argmax_u8, dim3(grid), dim3(kBlock), 0, ctx->stream, d_scores, ncells,
                        (unsigned long long)stride, (unsigned)cols, flat, recs);
     // one workgroup folds the records straight into pinned host memory
-    hipLaunchKernelGGL(argmax_fold, dim3(1), dim3(kBlock), 0, ctx->stream, recs, grid,
-                       static_cast<ArgmaxRecord *>(ctx->pinned));
+    ArgmaxRecord *h_rec = pinned_at<ArgmaxRecord>(ctx, kPinRecord);
+    hipLaunchKernelGGL(argmax_fold, dim3(1), dim3(kBlock), 0, ctx->stream, recs, grid, h_rec);
     LM_HIP_TRY(hipGetLastError());
     LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = *static_cast<const ArgmaxRecord *>(ctx->pinned);
+    *out = *h_rec;
     return LM_HIP_OK;
 }
 
@@ -202,9 +202,8 @@ int launch_threshold_u8(lm_hip_ctx *ctx, const uint8_t *d_scores, size_t rows, s
     hipLaunchKernelGGL(threshold_count_u8, dim3((unsigned)nchunks), dim3(kBlock), 0, ctx->stream, d_scores,
                        ncells, (unsigned long long)stride, (unsigned)cols, flat, t, counts);
     LM_TRY(launch_scan_u32(ctx, counts, nchunks, offsets, tiles, total));
-    LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const unsigned long long count = *static_cast<unsigned long long *>(ctx->pinned);
+    unsigned long long count = 0;
+    LM_TRY(read_back(ctx, ctx->stream, total, &count));
     if (count == 0)
         return LM_HIP_OK;
     lm_hip_coords *host = static_cast<lm_hip_coords *>(result_alloc(count * sizeof(lm_hip_coords)));

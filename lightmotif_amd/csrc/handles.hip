@@ -256,13 +256,14 @@ static int ingest_tiled(lm_hip_ctx *ctx, const uint8_t *host, size_t len, size_t
             return give_up(st);
         e = hipEventRecord(ctx->tile_consumed[b], ctx->stream);
     }
+    unsigned long long *h_bad = pinned_at<unsigned long long>(ctx, kPinCounters);  // (read_back, with this call's own error text)
     if (e == hipSuccess)
-        e = hipMemcpyAsync(ctx->pinned, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream);
+        e = hipMemcpyAsync(h_bad, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
         return give_up(fail(LM_HIP_ERR_HIP, "%s: upload failed: %s", what, hipGetErrorString(e)));
-    const unsigned long long bad = *static_cast<unsigned long long *>(ctx->pinned);
+    const unsigned long long bad = *h_bad;
     if (bad != ~0ull) {
         lm_hip_seq_destroy(s);
         if (bad_index)
@@ -588,7 +589,7 @@ int lm::score_store_tracked(lm_hip_ctx *ctx, const ScoreArgs &a, lm_hip_scores *
     if ((row_end - row_begin) * a.cols < (8u << 20)) {
         // small inputs are launch-latency bound: ONE launch stores, tracks the best cell and folds the
         // workgroup records (MODE_STORE_TRACK), and leaves the record in pinned memory as well
-        const unsigned gen = ++scores->best_generation ? scores->best_generation : ++scores->best_generation;  // never 0
+        const unsigned gen = next_generation(scores->best_generation);
         LM_TRY(launch_score_store_track(ctx, a, scores->d_best, scores->h_best, gen, &tracked,
                                         scores->first_cell_rule ? 1 : 0, ctx->host_fold ? scores : nullptr));
         scores->best_valid = tracked;   // false when the records went to the host (scores->records_on_host)
@@ -639,26 +640,15 @@ int lm_hip_argmax(lm_hip_ctx *ctx, const lm_hip_scores *s, int *found, lm_hip_co
             // behind it: poll that (a PCIe write after the fold) rather than wait for the completion signal of the
             // kernel -- ~10 us of every 22 us iteration of the reference's bench loop (dna.rs:104-107).  A kernel
             // that never gets there (a fault) is caught by the bounded spin: the stream is synchronised instead.
-            const volatile unsigned *gen = reinterpret_cast<const volatile unsigned *>(s->h_best + 1);
-            bool seen = false;
-            for (unsigned spin = 0; spin < (1u << 20); ++spin) {  // tens of milliseconds at most
-                if (__atomic_load_n(gen, __ATOMIC_ACQUIRE) == s->best_generation) {
-                    seen = true;
-                    break;
-                }
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-                __builtin_ia32_pause();
-#endif
-            }
-            if (!seen)
+            if (!poll_generation(reinterpret_cast<const volatile unsigned *>(s->h_best + 1), s->best_generation))  // tens of milliseconds at most
                 LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
             record_to_coords(*s->h_best, s->cols, found, best, value);
             return LM_HIP_OK;
         }
-        LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, s->d_best, sizeof(ArgmaxRecord), hipMemcpyDeviceToHost,
-                                  ctx->stream));
+        ArgmaxRecord *h_rec = pinned_at<ArgmaxRecord>(ctx, kPinRecord);
+        LM_HIP_TRY(hipMemcpyAsync(h_rec, s->d_best, sizeof(ArgmaxRecord), hipMemcpyDeviceToHost, ctx->stream));
         LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        record_to_coords(*static_cast<const ArgmaxRecord *>(ctx->pinned), s->cols, found, best, value);
+        record_to_coords(*h_rec, s->cols, found, best, value);
         return LM_HIP_OK;
     }
     return lm_hip_argmax_shard_f32_dptr(ctx, s->d_data, s->rows, s->stride, s->cols, s->first_cell_rule ? 1 : 0,

@@ -524,19 +524,16 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     // speculative form: the staging block -- counters | abort flag | starts | head of the list --
     // lives in the context's pinned host buffer and the kernels write it THERE (posted writes
     // over PCIe, visible after the stream synchronisation): no copy command, no memset
-    const size_t p_abort = 16, p_starts = 32;
+    const size_t p_abort = 16, p_done = 24, p_starts = 32;
     const size_t p_out = p_starts + align16((njobs + 1) * 8);
     const size_t p_values = p_out + align16(pre * (cut ? sizeof(lm_hip_set_hit) : rec_bytes));
     const size_t p_bytes = p_values + align16(pre * sizeof(float));
-    char *pin = static_cast<char *>(ctx->pinned);
+    char *pin = pinned_at<char>(ctx, kPinHitStaging, 0);  // (the exact form reads back through kPinHitReadback, the same bytes)
     static_assert(sizeof(size_t) == 8, "job offsets are read back as 64-bit values");
     const size_t starts_bytes = (njobs + 1) * 8;
-    if (speculative && p_bytes > kPinnedBytes / 2) {
+    if (speculative && !pinned_at<char>(ctx, kPinHitStaging, p_bytes)) {
         *status = 2;  // too many jobs for the staging block: the caller runs the exact form
-        LM_HIP_TRY(hipMemcpyAsync(pin, d_counters, 16, hipMemcpyDeviceToHost, ctx->stream));
-        LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        counts_out[0] = reinterpret_cast<unsigned long long *>(pin)[0];
-        counts_out[1] = reinterpret_cast<unsigned long long *>(pin)[1];
+        LM_TRY(read_back_counters(ctx, ctx->stream, d_counters, counts_out));
         if (counts_out[0] > cap || counts_out[1] > cand_cap)
             *status = 1;
         return LM_HIP_OK;
@@ -582,8 +579,8 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     unsigned generation = 0;
     if (short_form && speculative && ctx->poll_done) {
         done_ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ctx->d_short) + kShortOffTicket);
-        done_flag = reinterpret_cast<unsigned *>(pin + 24);
-        generation = ++ctx->short_generation ? ctx->short_generation : ++ctx->short_generation;  // never 0
+        done_flag = reinterpret_cast<unsigned *>(pin + p_done);
+        generation = next_generation(ctx->short_generation);
     }
     const unsigned grid = (unsigned)std::max<unsigned long long>(
         std::min<unsigned long long>((sized_for + kBlock - 1) / kBlock, (unsigned long long)ctx->num_cus * 32), 1);
@@ -670,8 +667,8 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
         // the read-back of the compacted list: as below, with the survivors' count = the last of the new starts
         if (speculative) {
             LM_HIP_TRY(hipStreamSynchronize(st));
-            counts_out[0] = reinterpret_cast<unsigned long long *>(pin)[0];
-            counts_out[1] = reinterpret_cast<unsigned long long *>(pin)[1];
+            counts_out[0] = header[0];
+            counts_out[1] = header[1];
             if (counts_out[0] > cap || counts_out[1] > cand_cap) {
                 *status = 1;
                 return LM_HIP_OK;
@@ -711,25 +708,14 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
         return LM_HIP_OK;
     }
     if (speculative) {
-        bool seen = false;
-        if (done_flag) {  // the ranking kernel's last workgroup raises the word behind everything it and the others wrote
-            const volatile unsigned *flag = done_flag;
-            for (unsigned spin = 0; spin < (1u << 23); ++spin) {  // bounded: a kernel that never gets there is caught below
-                if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) == generation) {
-                    seen = true;
-                    break;
-                }
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-                __builtin_ia32_pause();
-#endif
-            }
-        }
+        // the ranking kernel's last workgroup raises the word behind everything it and the others wrote
+        const bool seen = done_flag && poll_generation(done_flag, generation, 1u << 23);  // bounded: a kernel that never gets there is caught below
         if (!seen || ctx->scan_timed)  // (option "time_scan": the events behind the kernels are read next -- they must have completed)
             LM_HIP_TRY(hipStreamSynchronize(st));
         if (short_form)
             ctx->short_dirty = false;  // both kernels ran: counts and cursors are zero again
-        counts_out[0] = reinterpret_cast<unsigned long long *>(pin)[0];
-        counts_out[1] = reinterpret_cast<unsigned long long *>(pin)[1];
+        counts_out[0] = header[0];
+        counts_out[1] = header[1];
         if (counts_out[0] > cap || counts_out[1] > cand_cap) {
             *status = 1;
             return LM_HIP_OK;
@@ -790,7 +776,7 @@ int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long lon
     // large ones go straight into the arrays handed to the caller.
     const size_t block_bytes = off_values + count * sizeof(float) - off_starts;
     hipError_t e;
-    if (block_bytes <= (256u << 10)) {
+    if (pinned_at<char>(ctx, kPinHitReadback, block_bytes)) {
         e = hipMemcpyAsync(pin, base + off_starts, block_bytes, hipMemcpyDeviceToHost, st);
         if (e == hipSuccess)
             e = hipStreamSynchronize(st);

@@ -1185,15 +1185,7 @@ int lm_hip_argmax_f32(const float *scores, size_t rows, size_t stride, size_t co
         lane_trim(lane);
         if (st != LM_HIP_OK)
             return st;
-        *found = rec.found;
-        if (rec.found) {
-            if (best) {
-                best->row = (size_t)(rec.index / (long long)cols);
-                best->col = (size_t)(rec.index % (long long)cols);
-            }
-            if (value)
-                *value = rec.value;
-        }
+        record_to_coords(rec, cols, found, best, value);
         return LM_HIP_OK;
     });
 }

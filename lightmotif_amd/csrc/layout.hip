@@ -96,9 +96,8 @@ int launch_encode(lm_hip_ctx *ctx, char alphabet, const uint8_t *d_ascii, size_t
                            (unsigned long long)len, alphabet == 'P' ? 1 : 0, lossy, d_dst, d_bad);
         LM_HIP_TRY(hipGetLastError());
     }
-    LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, d_bad, 8, hipMemcpyDeviceToHost, ctx->stream));
-    LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const unsigned long long bad = *static_cast<unsigned long long *>(ctx->pinned);
+    unsigned long long bad = 0;
+    LM_TRY(read_back(ctx, ctx->stream, d_bad, &bad));
     if (bad != ~0ull) {
         if (bad_index)
             *bad_index = (size_t)bad;
@@ -165,10 +164,7 @@ int launch_max_symbol(lm_hip_ctx *ctx, const uint8_t *d_data, size_t rows, size_
     hipLaunchKernelGGL(max_symbol_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, d_data,
                        (unsigned long long)rows, (unsigned long long)stride, (unsigned long long)cols, d_max);
     LM_HIP_TRY(hipGetLastError());
-    LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, d_max, 4, hipMemcpyDeviceToHost, ctx->stream));
-    LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *max_symbol = *static_cast<unsigned *>(ctx->pinned);
-    return LM_HIP_OK;
+    return read_back(ctx, ctx->stream, d_max, max_symbol);
 }
 
 // ---- stripe -------------------------------------------------------------------------------

@@ -68,7 +68,79 @@ struct ArgmaxRecord {
     long long index;  // flat index row * cols + col, -1 = none
 };
 
-constexpr size_t kPinnedBytes = 4u << 20;  // pinned staging buffer per context
+// ---- the context's pinned staging block -----------------------------------------
+//
+// Every context owns ONE page-locked, device-visible block of kPinnedBytes (allocated and released in context.hip).
+// Whatever returns something small to the host goes through it, so its users share it by the layout below: a region is
+// {offset, capacity} in bytes, and `pinned_at` is the only way to a pointer into the block.  A call holds ctx->mu from its
+// first use of the block to its last read, so regions only have to be disjoint where ONE call uses them together (the
+// static_asserts below); across calls a region's bytes are stale and every protocol that polls them clears them first.
+//
+//   region              bytes                    holds                                                    users
+//   kPinCounters        [0, 16)                  4 or 8 bytes read back (bad-symbol position, max         layout.hip, handles.hip (ingest), reduce.hip,
+//                                                symbol, hit total), or the {hits, candidates} pair       discrete.hip; score_threshold.hip, scanmax.hip,
+//                                                of a hit list (copied, or written by a kernel)           hits.hip, score_argmax.hip (candidate route)
+//   kPinRecord          [0, 64)                  one ArgmaxRecord written by a kernel or a copy; the      reduce.hip, discrete.hip, handles.hip;
+//                                                single-launch argmax raises its generation word          score_argmax.hip (result [0] of kPinArgmaxBatch
+//                                                right behind the record (byte 16)                        at n = 1)
+//   kPinArgmaxBatch     [0, whole)               exact fused argmax: ArgmaxRecord[n], then (64-byte       score_argmax.hip
+//                                                aligned) the FinalizeJob table the finalize kernel
+//                                                reads in place
+//   kPinCandResults     [16, half)               candidate-route argmax: ArgmaxRecord[jobs] behind the    score_argmax.hip
+//                                                counters, written by the reduction kernels
+//   kPinScanMaxState    [0, 256)                 Scanner::max window walk: ScanMaxState [0] written by    scanmax.hip
+//                                                the kernels, [1] the initial state staged for upload
+//   kPinListHead        [256, half)              Scanner::max by list: the first records of the           scanmax.hip
+//                                                unordered hit list, copied behind the counters
+//   kPinHitStaging      [0, half)                speculative ordering of a hit list: counters | abort     hits.hip (and through it the segment pass of
+//                                                flag (16) | done word (24) | job starts (32) | head      seqset.hip, which writes the head of ITS list)
+//                                                of the records | head of the values, kernel-written
+//   kPinHitReadback     [0, 256 KB)              exact ordering: starts | records | values of a short     hits.hip
+//                                                list in one copy
+//   kPinFoldRecords     [4096, whole)            single-job argmax: one 16-byte record per wavefront      score_argmax.hip
+//                                                + the first-cell slot, written by the scoring kernel
+//   kPinU8Out           [4096, half)             the u8 scores of a Scanner block, kernel-written         score_api.hip
+//   kPinUploadHead      [half, whole)            head of the device scratch block, assembled here and     score_plan.hip (upload_head: fused threshold and
+//                                                sent in one asynchronous copy                            candidate-route argmax)
+//   kPinCommBlock       [0, whole)               halo exchange: one 16-byte status word per rank;         comm.hip
+//                                                merges: the local record / count staged at [nranks],
+//                                                u64 counts [nranks] read back
+//   kPinCommGather      [0, half)                merges: MergeRecord[nranks] read back                    comm.hip
+//
+// The tracked store of score_into (score_store.hip, handles.hip) keeps its record and its wavefront records in pinned blocks
+// of the scores HANDLE, not here; it shares the generation and polling helpers below.
+constexpr size_t kPinnedBytes = 4u << 20;
+struct PinnedRegion {
+    size_t off, cap;
+    constexpr size_t end() const { return off + cap; }
+};
+constexpr PinnedRegion kPinCounters{0, 16};
+constexpr PinnedRegion kPinRecord{0, 64};
+constexpr size_t kPinGenerationWordOff = sizeof(ArgmaxRecord);  // in kPinRecord: the kernel raises the word at FusedOut::final_host + 1
+constexpr PinnedRegion kPinArgmaxBatch{0, kPinnedBytes};
+constexpr PinnedRegion kPinCandResults{16, kPinnedBytes / 2 - 16};
+constexpr PinnedRegion kPinScanMaxState{0, 256};
+constexpr PinnedRegion kPinListHead{256, kPinnedBytes / 2 - 256};
+constexpr PinnedRegion kPinHitStaging{0, kPinnedBytes / 2};
+constexpr PinnedRegion kPinHitReadback{0, 256u << 10};
+constexpr PinnedRegion kPinFoldRecords{4096, kPinnedBytes - 4096};
+constexpr PinnedRegion kPinU8Out{4096, kPinnedBytes / 2 - 4096};
+constexpr PinnedRegion kPinUploadHead{kPinnedBytes / 2, kPinnedBytes / 2};
+constexpr PinnedRegion kPinCommBlock{0, kPinnedBytes};
+constexpr PinnedRegion kPinCommGather{0, kPinnedBytes / 2};
+
+// regions one call uses together
+static_assert(kPinRecord.end() <= kPinFoldRecords.off, "single-job argmax: the record and its generation word lie before the wavefront records");
+static_assert(kPinCounters.end() <= kPinCandResults.off, "candidate-route argmax: the counters lie before the results");
+static_assert(kPinCandResults.end() <= kPinUploadHead.off, "candidate-route argmax: the results end where the uploaded head begins");
+static_assert(kPinCounters.end() <= kPinListHead.off, "Scanner::max by list: the counters lie before the head of the list");
+static_assert(kPinHitStaging.end() <= kPinUploadHead.off, "fused threshold: the kernels' staging ends where the uploaded head begins");
+static_assert(kPinHitReadback.end() <= kPinHitStaging.end(), "the exact ordering's read-back stays inside the staging of the speculative one");
+static_assert(kPinListHead.end() <= kPinUploadHead.off && kPinU8Out.end() <= kPinUploadHead.off, "the lower half's users stay in the lower half");
+// kPinArgmaxBatch and kPinFoldRecords extend past the half mark.  The region they must never meet is kPinUploadHead, whose
+// asynchronous copy may still be reading it; they cannot, because the exact argmax route (launch_score_argmax_exact) and
+// the tiled store kernel it may start with never call upload_head, and a call that does synchronises ctx->stream before it
+// returns.  kPinCommBlock (whole block) belongs to calls of comm.hip, which use nothing else of the block.
 
 // Host arrays handed to the caller (released with lm_hip_free = free).  Large ones are
 // 2 MB-aligned and marked for transparent huge pages: a fresh 50 MB block otherwise takes
@@ -98,8 +170,8 @@ struct lm_hip_ctx {
     lm::Scratch chunk_scores;   // fused reductions of sliced (M > 36) motifs: one chunk of f32 scores (score_launch.hpp)
     size_t chunk_rows = 1u << 22; // rows of that chunk (512 MB at C = 32; option "chunk_rows")
     bool chunked_fused = true;  // A/B knob: 0 = such motifs go cell by cell (option "chunked_fused")
-    void *pinned = nullptr;     // kPinnedBytes of host-pinned memory for read-backs
-    unsigned fold_generation = 0; // of the last single-job fused argmax whose kernel wrote its result into `pinned`
+    void *pinned = nullptr;     // the staging block: reached through lm::pinned_at and the layout above it alone
+    unsigned fold_generation = 0; // of the last single-job fused argmax whose kernel wrote its result into the staging block
     unsigned *d_ticket = nullptr; // "last workgroup folds the records" counter of the single-launch argmax forms (zero between launches)
     unsigned *d_short = nullptr;  // short hit lists (hits.hip, ShortOrder): bucket counts | cursors | zero tiles | offsets; counts and cursors are zero between calls
     unsigned short_generation = 0;  // of the last short ordering whose end the host polled (hits.hip: done_flag)
@@ -146,6 +218,68 @@ struct lm_hip_ctx {
 };
 
 namespace lm {
+// Region `r` of the staging block as T* for `count` elements that start `byte_off` bytes into it; nullptr: they do not fit.
+template <class T>
+inline T *pinned_at(const lm_hip_ctx *ctx, PinnedRegion r, size_t count = 1, size_t byte_off = 0)
+{
+    if (byte_off + count * sizeof(T) > r.cap)
+        return nullptr;
+    return reinterpret_cast<T *>(static_cast<char *>(ctx->pinned) + r.off + byte_off);
+}
+
+// One T from the device through kPinCounters: copy on `st`, synchronise, read.
+template <class T>
+inline int read_back(lm_hip_ctx *ctx, hipStream_t st, const void *d_src, T *out)
+{
+    static_assert(sizeof(T) <= kPinCounters.cap, "read_back is for a counter");
+    T *h = pinned_at<T>(ctx, kPinCounters);
+    LM_HIP_TRY(hipMemcpyAsync(h, d_src, sizeof(T), hipMemcpyDeviceToHost, st));
+    LM_HIP_TRY(hipStreamSynchronize(st));
+    *out = *h;
+    return LM_HIP_OK;
+}
+// ... the {hits, candidates} pair at the head of a hit list
+inline int read_back_counters(lm_hip_ctx *ctx, hipStream_t st, const void *d_counters, unsigned long long out[2])
+{
+    struct Pair { unsigned long long hits, candidates; } p{};
+    LM_TRY(read_back(ctx, st, d_counters, &p));
+    out[0] = p.hits;
+    out[1] = p.candidates;
+    return LM_HIP_OK;
+}
+
+// Generation words: a kernel raises one behind a result it writes into pinned memory, the host polls for the value it handed
+// to the launch.  0 is what cleared memory holds, so no launch gets it.
+inline unsigned next_generation(unsigned &g) { return ++g ? g : ++g; }
+// Bounded poll (a PCIe posted write lands a microsecond behind the kernel's last store, well before its completion signal);
+// false: not seen within `spins` loads -- the caller synchronises the stream instead, which also catches a faulted kernel.
+inline bool poll_generation(const volatile unsigned *word, unsigned generation, unsigned spins = 1u << 20)
+{
+    for (unsigned spin = 0; spin < spins; ++spin) {
+        if (__atomic_load_n(word, __ATOMIC_ACQUIRE) == generation)
+            return true;
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+        __builtin_ia32_pause();
+#endif
+    }
+    return false;
+}
+// The fold protocol of the single-launch argmax forms: advances ctx->fold_generation and, when `want_records`, clears the
+// nrec + 1 record slots of kPinFoldRecords (the block is shared staging: stale bytes must not look like this launch's
+// generation).  records == nullptr: not wanted, or they do not fit.
+struct FoldSlots {
+    uint4 *records;
+    unsigned generation;
+};
+inline FoldSlots begin_fold(lm_hip_ctx *ctx, size_t nrec, bool want_records = true)
+{
+    FoldSlots f{want_records ? pinned_at<uint4>(ctx, kPinFoldRecords, nrec + 1) : nullptr, next_generation(ctx->fold_generation)};
+    if (f.records)
+        for (size_t r = 0; r <= nrec; ++r)
+            reinterpret_cast<volatile unsigned long long *>(f.records)[2 * r] = 0ull;
+    return f;
+}
+
 // option "time_scan": the scan kernels of a fused call between two events on their stream, read after the call's
 // synchronisation (lm_hip_ctx_last_scan_kernel_ms).  Off: nothing is recorded.
 inline int scan_timer_begin(lm_hip_ctx *ctx, hipStream_t st)

@@ -156,10 +156,10 @@ int launch_argmax(lm_hip_ctx *ctx, const float *d_scores, size_t rows, size_t st
                   int first_cell_rule, ArgmaxRecord *out)
 {
     // the finalize kernel writes the record straight into pinned host memory
-    LM_TRY(launch_argmax_device(ctx, d_scores, rows, stride, cols, first_cell_rule,
-                                static_cast<ArgmaxRecord *>(ctx->pinned)));
+    ArgmaxRecord *h_rec = pinned_at<ArgmaxRecord>(ctx, kPinRecord);
+    LM_TRY(launch_argmax_device(ctx, d_scores, rows, stride, cols, first_cell_rule, h_rec));
     LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    *out = *static_cast<const ArgmaxRecord *>(ctx->pinned);
+    *out = *h_rec;
     return LM_HIP_OK;
 }
 
@@ -422,9 +422,8 @@ int launch_threshold(lm_hip_ctx *ctx, const float *d_scores, size_t rows, size_t
     hipLaunchKernelGGL(threshold_count, dim3((unsigned)nchunks), dim3(kBlock), 0, ctx->stream,
                        d_scores, ncells, (unsigned long long)stride, (unsigned)cols, flat, t, counts);
     LM_TRY(launch_scan_u32(ctx, counts, nchunks, offsets, tiles, total));
-    LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, total, 8, hipMemcpyDeviceToHost, ctx->stream));
-    LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    const unsigned long long count = *static_cast<unsigned long long *>(ctx->pinned);
+    unsigned long long count = 0;
+    LM_TRY(read_back(ctx, ctx->stream, total, &count));
     if (count == 0)
         return LM_HIP_OK;
 

@@ -380,10 +380,9 @@ static int scan_max_by_list(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_h
     // the host while a longer one goes through the device's ordering passes (hits.hip) -- one synchronisation instead of two
     // and no ordering launches for the ranges behind the first, which hold hundreds of records
     constexpr unsigned long long kHostSort = 4096;
-    char *pin = static_cast<char *>(ctx->pinned);
-    unsigned long long *h_counts = reinterpret_cast<unsigned long long *>(pin);
-    HitRecord *h_recs = reinterpret_cast<HitRecord *>(pin + 256);
-    static_assert(256 + kHostSort * sizeof(HitRecord) <= kPinnedBytes / 2, "the head of the list must fit the pinned block");
+    unsigned long long *h_counts = pinned_at<unsigned long long>(ctx, kPinCounters, 2);
+    HitRecord *h_recs = pinned_at<HitRecord>(ctx, kPinListHead, kHostSort);
+    static_assert(kHostSort * sizeof(HitRecord) <= kPinListHead.cap, "the head of the list must fit its region of the pinned block");
     LM_HIP_TRY(hipMemcpyAsync(h_counts, base, 16, hipMemcpyDeviceToHost, ctx->stream));
     LM_HIP_TRY(hipMemcpyAsync(h_recs, fo.hits, std::min(cap, kHostSort) * sizeof(HitRecord), hipMemcpyDeviceToHost, ctx->stream));
     LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -494,7 +493,8 @@ int launch_scan_max(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_hip_seq *
     LM_TRY(ctx->scan_buf.reserve(d_bytes + 256));
     uint8_t *d_d = static_cast<uint8_t *>(ctx->scan_buf.ptr);
     ScanMaxState *d_st = reinterpret_cast<ScanMaxState *>(d_d + d_bytes);
-    ScanMaxState *h_st = static_cast<ScanMaxState *>(ctx->pinned);
+    ScanMaxState *h_st = pinned_at<ScanMaxState>(ctx, kPinScanMaxState, 2);
+    static_assert(2 * sizeof(ScanMaxState) <= kPinScanMaxState.cap, "the walk's two states must fit their region of the pinned block");
     ScanMaxState init{};
     init.index = position;
     init.cursor = 0;

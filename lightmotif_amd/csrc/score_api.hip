@@ -101,10 +101,10 @@ int lm_hip_score_u8(lm_hip_ctx *ctx, const uint8_t *weights, size_t m, size_t we
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard guard(ctx->device);
     const size_t nrows = row_end - row_begin, cols = seq->cols;
-    if (nrows * cols + 4096 <= kPinnedBytes / 2 && nrows * cols <= (128u << 10)) {
+    uint8_t *z_out = nrows * cols <= (128u << 10) ? pinned_at<uint8_t>(ctx, kPinU8Out, nrows * cols) : nullptr;
+    if (z_out) {
         // a Scanner block (scan.rs:174-178: 256 rows): the kernel writes the u8 scores straight into pinned host
         // memory -- no copy command, one synchronisation (tools/kbench/hostpipe_bench.hip: 16 us against 28 us)
-        uint8_t *z_out = static_cast<uint8_t *>(ctx->pinned) + 4096;
         DiscreteArgs a{weights, m, weights_stride, k, seq->d_data, seq->stride, cols, row_begin, row_end, z_out, cols,
                        saturate != 0};
         LM_TRY(launch_score_u8(ctx, a));
@@ -143,15 +143,9 @@ int lm_hip_argmax_u8_dptr(lm_hip_ctx *ctx, const uint8_t *d_scores, size_t rows,
     DeviceGuard guard(ctx->device);
     ArgmaxRecord rec{};
     LM_TRY(launch_argmax_u8(ctx, d_scores, rows, stride, cols, &rec));
-    *found = rec.found;
-    if (rec.found) {
-        if (best) {
-            best->row = (size_t)(rec.index / (long long)cols);
-            best->col = (size_t)(rec.index % (long long)cols);
-        }
-        if (value)
-            *value = (uint8_t)rec.value;
-    }
+    record_to_coords(rec, cols, found, best, nullptr);
+    if (rec.found && value)
+        *value = (uint8_t)rec.value;
     return LM_HIP_OK;
 }
 
@@ -302,6 +296,25 @@ static int batch_jobs(const lm_hip_pssm *const *pssms, size_t n, const lm_hip_se
     return LM_HIP_OK;
 }
 
+// The jobs that have scores (not degenerate), in caller order, with their indices and (optional) thresholds.
+struct LiveJobs {
+    std::vector<ScoreArgs> jobs;
+    std::vector<float> t;
+    std::vector<size_t> idx;
+};
+static LiveJobs live_jobs(const std::vector<ScoreArgs> &jobs, const std::vector<char> &degenerate, const float *thresholds)
+{
+    LiveJobs live;
+    for (size_t i = 0; i < jobs.size(); ++i)
+        if (!degenerate[i]) {
+            live.jobs.push_back(jobs[i]);
+            if (thresholds)
+                live.t.push_back(thresholds[i]);
+            live.idx.push_back(i);
+        }
+    return live;
+}
+
 int lm_hip_scan_argmax_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n,
                              const lm_hip_seq *seq, int *found, lm_hip_coords *best, float *value)
 {
@@ -310,23 +323,16 @@ int lm_hip_scan_argmax_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, s
     std::vector<ScoreArgs> jobs;
     std::vector<char> degenerate;
     LM_TRY(batch_jobs(pssms, n, seq, &jobs, &degenerate));
-    std::vector<ScoreArgs> live;
-    std::vector<size_t> live_idx;
-    for (size_t i = 0; i < n; ++i) {
-        found[i] = 0;
-        if (!degenerate[i]) {
-            live.push_back(jobs[i]);
-            live_idx.push_back(i);
-        }
-    }
-    if (live.empty())
+    std::fill_n(found, n, 0);
+    const LiveJobs live = live_jobs(jobs, degenerate, nullptr);
+    if (live.jobs.empty())
         return LM_HIP_OK;
     std::lock_guard<std::mutex> lock(ctx->mu);
     DeviceGuard guard(ctx->device);
-    std::vector<ArgmaxRecord> recs(live.size());
-    LM_TRY(launch_score_argmax_batch(ctx, live.data(), live.size(), 1, recs.data()));
-    for (size_t k = 0; k < live.size(); ++k) {
-        const size_t i = live_idx[k];
+    std::vector<ArgmaxRecord> recs(live.jobs.size());
+    LM_TRY(launch_score_argmax_batch(ctx, live.jobs.data(), live.jobs.size(), 1, recs.data()));
+    for (size_t k = 0; k < live.jobs.size(); ++k) {
+        const size_t i = live.idx[k];
         record_to_coords(recs[k], seq->cols, &found[i], best ? &best[i] : nullptr,
                          value ? &value[i] : nullptr);
     }
@@ -345,30 +351,21 @@ int lm_hip_scan_threshold_batch(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms
     std::vector<ScoreArgs> jobs;
     std::vector<char> degenerate;
     LM_TRY(batch_jobs(pssms, n, seq, &jobs, &degenerate));
-    std::vector<ScoreArgs> live;
-    std::vector<float> live_t;
-    std::vector<size_t> live_idx;
-    for (size_t i = 0; i < n; ++i) {
-        counts[i] = 0;
-        if (!degenerate[i]) {
-            live.push_back(jobs[i]);
-            live_t.push_back(thresholds[i]);
-            live_idx.push_back(i);
-        }
-    }
-    if (live.empty())
+    std::fill_n(counts, n, (size_t)0);
+    const LiveJobs live = live_jobs(jobs, degenerate, thresholds);
+    if (live.jobs.empty())
         return LM_HIP_OK;
     HitOutput ho;
     {
         std::lock_guard<std::mutex> lock(ctx->mu);
         DeviceGuard guard(ctx->device);
         ScratchTrim trim(ctx);
-        LM_TRY(launch_score_threshold_batch(ctx, live.data(), live_t.data(), live.size(),
+        LM_TRY(launch_score_threshold_batch(ctx, live.jobs.data(), live.t.data(), live.jobs.size(),
                                             HitKeys::RowMajor, &ho));
     }
     // live jobs are in caller order, so the concatenated list already is the output
-    for (size_t k = 0; k < live.size(); ++k)
-        counts[live_idx[k]] = ho.job_start[k + 1] - ho.job_start[k];
+    for (size_t k = 0; k < live.jobs.size(); ++k)
+        counts[live.idx[k]] = ho.job_start[k + 1] - ho.job_start[k];
     *coords = ho.coords;
     if (values)
         *values = ho.values;
@@ -391,18 +388,9 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
     std::vector<ScoreArgs> jobs;
     std::vector<char> degenerate;
     LM_TRY(batch_jobs(pssms, n, seq, &jobs, &degenerate));
-    std::vector<ScoreArgs> live;
-    std::vector<float> live_t;
-    std::vector<size_t> live_idx;
-    for (size_t i = 0; i < n; ++i) {
-        counts[i] = 0;
-        if (!degenerate[i]) {
-            live.push_back(jobs[i]);
-            live_t.push_back(thresholds[i]);
-            live_idx.push_back(i);
-        }
-    }
-    if (live.empty())
+    std::fill_n(counts, n, (size_t)0);
+    const LiveJobs live = live_jobs(jobs, degenerate, thresholds);
+    if (live.jobs.empty())
         return LM_HIP_OK;
     SegmentCut cut;
     cut.d_offsets = set->d_offsets;
@@ -412,10 +400,10 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
         std::lock_guard<std::mutex> lock(ctx->mu);
         DeviceGuard guard(ctx->device);
         ScratchTrim trim(ctx);
-        LM_TRY(launch_score_threshold_batch(ctx, live.data(), live_t.data(), live.size(), HitKeys::Position, &ho, &cut));
+        LM_TRY(launch_score_threshold_batch(ctx, live.jobs.data(), live.t.data(), live.jobs.size(), HitKeys::Position, &ho, &cut));
     }
-    for (size_t k = 0; k < live.size(); ++k)
-        counts[live_idx[k]] = ho.job_start[k + 1] - ho.job_start[k];
+    for (size_t k = 0; k < live.jobs.size(); ++k)
+        counts[live.idx[k]] = ho.job_start[k + 1] - ho.job_start[k];
     *hits = ho.set_hits;
     return LM_HIP_OK;
 }

@@ -93,44 +93,89 @@ __global__ __launch_bounds__(kBlock) void argmax_finalize_batch(const FinalizeJo
     }
 }
 
+// One small job off the C = 32 kernels (C = 1 is the Generic geometry of the reference's own bench, dna.rs:112-116):
+// ONE launch.  The tiled store kernel scores into the chunk buffer and leaves a (value, cell) record per workgroup
+// in the pinned block, folded here -- what score_into + argmax on handles do (27 us per iteration of configs[0]);
+// the chunked route takes a store, a reduction and a finalize launch (41 us).  *done = false: the shape is not this
+// route's, or the kernel left no records (the stream is then quiescent) -- the general route takes the job.
+// (C = 16 has an unrolled store kernel of its own, which leaves no records)
+static int argmax_tiled_host_fold(lm_hip_ctx *ctx, const ScoreArgs &a, int first_cell_rule, ArgmaxRecord *out, bool *done)
+{
+    *done = false;
+    if (!ctx->host_fold || a.cols == 32 || a.cols == 16 || !chunked_ok(ctx, a) || plan_c32(ctx, a, false).ok)
+        return LM_HIP_OK;
+    const unsigned long long rows = a.row_end - a.row_begin;
+    const unsigned nrec = tiled_records(ctx, a);
+    if (!nrec || rows > chunk_rows_for(ctx, a) || rows * a.cols >= (1ull << 32) || !pinned_at<uint4>(ctx, kPinFoldRecords, (size_t)nrec + 1))
+        return LM_HIP_OK;
+    LM_TRY(ctx->chunk_scores.reserve(rows * a.cols * sizeof(float)));
+    const FoldSlots fold = begin_fold(ctx, nrec);
+    unsigned written = 0;
+    ScoreArgs t = a;
+    t.d_out = static_cast<float *>(ctx->chunk_scores.ptr);
+    t.out_stride = a.cols;
+    t.track_records = fold.records;
+    t.track_generation = fold.generation;
+    t.track_cap = (size_t)nrec + 1;
+    t.track_nrec = &written;
+    LM_TRY(launch_score_store(ctx, t));
+    if (!written) {
+        LM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // (no records after all: the general route, buffer quiescent)
+        return LM_HIP_OK;
+    }
+    ctx->last_kernel = "score_tiled+host_fold";
+    *done = true;
+    return fold_host_records(ctx, fold.records, written, fold.generation, first_cell_rule != 0, out);
+}
+
+// Where the results and the FinalizeJob table of an exact argmax call live.  Small batches skip both copies: the job
+// table is written into the context's pinned (device-visible) block (kPinArgmaxBatch), the finalize kernel reads it
+// from there and writes the results in front of it, and the host reads them after the one synchronisation.  A single
+// short scan is launch-latency bound, so the two staged copies were a third of its wall time.  Otherwise both live in
+// the device scratch around the block records and travel by copy commands.
+struct ArgmaxDelivery {
+    bool zero_copy;
+    ArgmaxRecord *results;  // [n], where the kernels write them; at n = 1 the generation word follows results[0]
+    FinalizeJob *d_jobs;    // [n], where the finalize kernel reads the table
+    FinalizeJob *fj;        // [n], where the host fills it in (zero_copy: d_jobs itself)
+    std::vector<FinalizeJob> fj_heap;
+};
+static constexpr size_t pinned_jobs_off(size_t n) { return (sizeof(ArgmaxRecord) * n + 63) / 64 * 64; }
+static_assert(pinned_jobs_off(1) >= kPinRecord.end() && pinned_jobs_off(1) + sizeof(FinalizeJob) <= kPinFoldRecords.off,
+              "single-job argmax: the job table lies between the record with its generation word and the wavefront records");
+
+static ArgmaxDelivery argmax_delivery(lm_hip_ctx *ctx, size_t n, char *scratch_base, size_t off_jobs)
+{
+    ArgmaxDelivery d{};
+    d.results = reinterpret_cast<ArgmaxRecord *>(scratch_base);
+    d.d_jobs = reinterpret_cast<FinalizeJob *>(scratch_base + off_jobs);
+    FinalizeJob *pin_jobs = pinned_at<FinalizeJob>(ctx, kPinArgmaxBatch, n, pinned_jobs_off(n));
+    d.zero_copy = pin_jobs != nullptr;
+    if (d.zero_copy) {
+        d.d_jobs = d.fj = pin_jobs;
+        d.results = pinned_at<ArgmaxRecord>(ctx, kPinArgmaxBatch, n);
+    } else {
+        d.fj_heap.resize(n);
+        d.fj = d.fj_heap.data();
+    }
+    return d;
+}
+
 // Fused score+argmax of `n` independent jobs (one motif each): the n scoring kernels
 // are enqueued back to back, each leaving per-workgroup records in its own region,
 // then ONE finalize launch reduces every job and ONE synchronisation returns.
+// A single job through the exact kernel is delivered without the finalize launch (fold_in_kernel below): by the
+// host's fold of the wavefronts' records, or by the record its last workgroup writes and the host polls for.
 static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
                                      int first_cell_rule, ArgmaxRecord *out)
 {
     if (n == 0)
         return LM_HIP_OK;
-    // One small job off the C = 32 kernels (C = 1 is the Generic geometry of the reference's own bench, dna.rs:112-116):
-    // ONE launch.  The tiled store kernel scores into the chunk buffer and leaves a (value, cell) record per workgroup
-    // in the pinned block, folded here -- what score_into + argmax on handles do (27 us per iteration of configs[0]);
-    // the chunked route below takes a store, a reduction and a finalize launch (41 us).
-    // (C = 16 has an unrolled store kernel of its own, which leaves no records)
-    if (n == 1 && ctx->host_fold && jobs[0].cols != 32 && jobs[0].cols != 16 && chunked_ok(ctx, jobs[0]) && !plan_c32(ctx, jobs[0], false).ok) {
-        const ScoreArgs &a = jobs[0];
-        const unsigned long long rows = a.row_end - a.row_begin;
-        const unsigned nrec = tiled_records(ctx, a);
-        if (nrec && rows <= chunk_rows_for(ctx, a) && rows * a.cols < (1ull << 32) && 4096 + ((size_t)nrec + 1) * 16 <= kPinnedBytes) {
-            LM_TRY(ctx->chunk_scores.reserve(rows * a.cols * sizeof(float)));
-            uint4 *records = reinterpret_cast<uint4 *>(static_cast<char *>(ctx->pinned) + 4096);
-            for (size_t r = 0; r <= nrec; ++r)  // shared staging: stale bytes must not look like this launch's generation
-                reinterpret_cast<volatile unsigned long long *>(records)[2 * r] = 0ull;
-            const unsigned gen = ++ctx->fold_generation ? ctx->fold_generation : ++ctx->fold_generation;
-            unsigned written = 0;
-            ScoreArgs t = a;
-            t.d_out = static_cast<float *>(ctx->chunk_scores.ptr);
-            t.out_stride = a.cols;
-            t.track_records = records;
-            t.track_generation = gen;
-            t.track_cap = (size_t)nrec + 1;
-            t.track_nrec = &written;
-            LM_TRY(launch_score_store(ctx, t));
-            if (written) {
-                ctx->last_kernel = "score_tiled+host_fold";
-                return fold_host_records(ctx, records, written, gen, first_cell_rule != 0, out);
-            }
-            LM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // (no records after all: the general route, buffer quiescent)
-        }
+    if (n == 1) {
+        bool done = false;
+        LM_TRY(argmax_tiled_host_fold(ctx, jobs[0], first_cell_rule, out, &done));
+        if (done)
+            return LM_HIP_OK;
     }
     const std::vector<JobGroup> groups = group_jobs(ctx, jobs, n, [&](size_t i) {
         return plan_c32(ctx, jobs[i], false).ok ? KIND_EXACT : chunked_ok(ctx, jobs[i]) ? KIND_CHUNKED : KIND_GENERIC;
@@ -148,28 +193,13 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
                                                 : g.plan.grid.x;
             total_blocks += grids[i];
         }
+    // device scratch: results | block records | job table
     const size_t off_blocks = sizeof(ArgmaxRecord) * n;
     const size_t off_jobs = off_blocks + sizeof(ArgmaxRecord) * total_blocks;
     LM_TRY(ctx->scratch.reserve(off_jobs + sizeof(FinalizeJob) * n));
     char *base = static_cast<char *>(ctx->scratch.ptr);
-    ArgmaxRecord *results = reinterpret_cast<ArgmaxRecord *>(base);
     ArgmaxRecord *blocks = reinterpret_cast<ArgmaxRecord *>(base + off_blocks);
-    FinalizeJob *d_jobs = reinterpret_cast<FinalizeJob *>(base + off_jobs);
-    // Small batches skip both copies: the job table is written into the context's
-    // pinned (device-visible) buffer, the finalize kernel reads it from there and
-    // writes the results next to it, and the host reads them after the one
-    // synchronisation.  A single short scan is launch-latency bound, so the two
-    // staged copies were a third of its wall time.
-    const size_t pin_jobs_off = (sizeof(ArgmaxRecord) * n + 63) / 64 * 64;
-    const bool zero_copy = pin_jobs_off + sizeof(FinalizeJob) * n <= kPinnedBytes;
-    std::vector<FinalizeJob> fj_heap(zero_copy ? 0 : n);
-    FinalizeJob *fj = zero_copy
-                          ? reinterpret_cast<FinalizeJob *>(static_cast<char *>(ctx->pinned) + pin_jobs_off)
-                          : fj_heap.data();
-    if (zero_copy) {
-        d_jobs = fj;
-        results = static_cast<ArgmaxRecord *>(ctx->pinned);
-    }
+    const ArgmaxDelivery dv = argmax_delivery(ctx, n, base, off_jobs);
     // block records: job i owns grids[i] records starting at block_pos[i]
     std::vector<size_t> block_pos(n);
     {
@@ -195,9 +225,10 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
     LM_TRY(streams.fork());
     // one job through the exact kernel: its last workgroup folds the records and writes the result straight
     // into the pinned block -- one launch instead of two (a small scan is launch-latency bound)
-    const bool fold_in_kernel = n == 1 && groups.size() == 1 && groups[0].kind == KIND_EXACT && zero_copy;
-    uint4 *host_records = nullptr;  // fold_in_kernel, small job: the wavefronts' records in the pinned block
+    const bool fold_in_kernel = n == 1 && groups.size() == 1 && groups[0].kind == KIND_EXACT && dv.zero_copy;
+    FoldSlots fold{nullptr, 0};  // fold_in_kernel: the launch's generation; small job: the wavefronts' records in the pinned block
     unsigned host_nrec = 0;
+    volatile unsigned *gen_word = pinned_at<volatile unsigned>(ctx, kPinRecord, 1, kPinGenerationWordOff);
     if (fold_in_kernel)
         LM_TRY(ensure_ticket(ctx));
     for (size_t gi = 0; gi < groups.size(); ++gi) {
@@ -207,24 +238,19 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
         FusedOut fo{};
         fo.block_best = blocks + block_pos[g.idx[0]];
         if (fold_in_kernel) {
-            fo.ticket = ctx->d_ticket;
-            fo.final_out = reinterpret_cast<ArgmaxRecord *>(ctx->d_ticket + 4);  // device copy nobody reads: 16 spare bytes
-            fo.final_host = results;                                             // pinned: record, then the generation word
-            fo.generation = ++ctx->fold_generation ? ctx->fold_generation : ++ctx->fold_generation;
-            *reinterpret_cast<volatile unsigned *>(results + 1) = 0u;  // (the block is shared staging: no stale match)
-            fo.first_cell_rule = first_cell_rule;
             // few wavefronts and 32-bit cell indices: no fold on the device, the wavefronts' records go straight
-            // into the pinned block (from byte 4096 on) and are folded below
+            // into the pinned block (kPinFoldRecords) and are folded below
             const size_t nrec = (size_t)g.plan.grid.x * (kBlock / 64);
             const unsigned long long ncells = (unsigned long long)(a.row_end - a.row_begin) * a.cols;
-            if (ctx->host_fold && ncells < (1ull << 32) && 4096 + (nrec + 1) * 16 <= kPinnedBytes) {
-                host_records = reinterpret_cast<uint4 *>(static_cast<char *>(ctx->pinned) + 4096);
-                host_nrec = (unsigned)nrec;
-                // the block is shared staging: stale bytes must not look like this launch's generation
-                for (size_t r = 0; r <= nrec; ++r)
-                    reinterpret_cast<volatile unsigned long long *>(host_records)[2 * r] = 0ull;
-                fo.host_records = host_records;
-            }
+            fold = begin_fold(ctx, nrec, ctx->host_fold && ncells < (1ull << 32));
+            host_nrec = fold.records ? (unsigned)nrec : 0u;
+            fo.ticket = ctx->d_ticket;
+            fo.final_out = reinterpret_cast<ArgmaxRecord *>(ctx->d_ticket + 4);  // device copy nobody reads: 16 spare bytes
+            fo.final_host = dv.results;                                          // pinned: record, then the generation word
+            fo.generation = fold.generation;
+            *gen_word = 0u;  // (the block is shared staging: no stale match)
+            fo.first_cell_rule = first_cell_rule;
+            fo.host_records = fold.records;
         }
         if (g.kind == KIND_EXACT) {
             fo.batch = n > 1 ? d_bparams + sp.groups[gi].pos : nullptr;
@@ -245,43 +271,37 @@ static int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, siz
     }
     for (size_t i = 0; i < n; ++i) {
         const ScoreArgs &a = jobs[i];
-        fj[i] = FinalizeJob{blocks + block_pos[i], grids[i], (int)a.pssm->m, (int)a.pssm->k,
-                            a.d_seq + a.row_begin * a.seq_stride,
-                            (unsigned long long)a.seq_stride, a.pssm->d_dense};
+        dv.fj[i] = FinalizeJob{blocks + block_pos[i], grids[i], (int)a.pssm->m, (int)a.pssm->k,
+                               a.d_seq + a.row_begin * a.seq_stride,
+                               (unsigned long long)a.seq_stride, a.pssm->d_dense};
     }
     LM_TRY(streams.join());
-    if (!zero_copy)
-        LM_HIP_TRY(hipMemcpyAsync(d_jobs, fj, sizeof(FinalizeJob) * n, hipMemcpyHostToDevice,
+    if (!dv.zero_copy)
+        LM_HIP_TRY(hipMemcpyAsync(dv.d_jobs, dv.fj, sizeof(FinalizeJob) * n, hipMemcpyHostToDevice,
                                   ctx->stream));
     if (!fold_in_kernel) {
         hipLaunchKernelGGL(argmax_finalize_batch, dim3((unsigned)n), dim3(kBlock), 0, ctx->stream,
-                           d_jobs, first_cell_rule, results);
+                           dv.d_jobs, first_cell_rule, dv.results);
         LM_HIP_TRY(hipGetLastError());
     }
-    if (!zero_copy)
-        LM_HIP_TRY(hipMemcpyAsync(out, results, sizeof(ArgmaxRecord) * n, hipMemcpyDeviceToHost,
+    if (!dv.zero_copy)
+        LM_HIP_TRY(hipMemcpyAsync(out, dv.results, sizeof(ArgmaxRecord) * n, hipMemcpyDeviceToHost,
                                   ctx->stream));
-    if (fold_in_kernel && host_records)
-        return fold_host_records(ctx, host_records, host_nrec, ctx->fold_generation, first_cell_rule != 0, out);
+    // delivery: (1) the host folds the wavefronts' records
+    if (fold_in_kernel && fold.records)
+        return fold_host_records(ctx, fold.records, host_nrec, fold.generation, first_cell_rule != 0, out);
+    // (2) the kernel raises the generation word behind the pinned record once it is written: poll it instead of
+    // waiting for the kernel's completion signal; bounded, then synchronise
     if (fold_in_kernel) {
-        // the kernel raises the generation word behind the pinned record once it is written: poll it (a PCIe write
-        // after the fold) instead of waiting for the kernel's completion signal; bounded, then synchronise
-        const volatile unsigned *gen = reinterpret_cast<const volatile unsigned *>(results + 1);
-        bool seen = false;
-        for (unsigned spin = 0; spin < (1u << 20) && !seen; ++spin) {
-            seen = __atomic_load_n(gen, __ATOMIC_ACQUIRE) == ctx->fold_generation;
-#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
-            __builtin_ia32_pause();
-#endif
-        }
-        if (!seen)
+        if (!poll_generation(gen_word, fold.generation))
             LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        memcpy(out, results, sizeof(ArgmaxRecord));
+        memcpy(out, dv.results, sizeof(ArgmaxRecord));
         return LM_HIP_OK;
     }
+    // (3) the finalize launch
     LM_HIP_TRY(hipStreamSynchronize(ctx->stream));  // also keeps `fj` alive long enough
-    if (zero_copy)
-        memcpy(out, results, sizeof(ArgmaxRecord) * n);
+    if (dv.zero_copy)
+        memcpy(out, dv.results, sizeof(ArgmaxRecord) * n);
     return LM_HIP_OK;
 }
 
@@ -712,11 +732,13 @@ static int argmax_by_prefilter(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
     fo.batch = nullptr;
     LM_TRY(launch_rescore(ctx, st, d_rj, fo, rj.data(), npos));
     // results and the two list counters are written straight into the pinned buffer's lower half
-    const bool pin = 16 + npos * sizeof(ArgmaxRecord) <= kPinnedBytes / 2;
-    ArgmaxRecord *res = pin ? reinterpret_cast<ArgmaxRecord *>(static_cast<char *>(ctx->pinned) + 16) : d_res;
+    unsigned long long *h_counts = pinned_at<unsigned long long>(ctx, kPinCounters, 2);
+    ArgmaxRecord *pin_res = pinned_at<ArgmaxRecord>(ctx, kPinCandResults, npos);
+    const bool pin = pin_res != nullptr;
+    ArgmaxRecord *res = pin ? pin_res : d_res;
     if (npos == 1) {
         hipLaunchKernelGGL(hits_best_single, dim3(1), dim3(kBestSingleBlock), 0, st, fo.hits, fo.hit_count, cap, res,
-                           pin ? static_cast<unsigned long long *>(ctx->pinned) : static_cast<unsigned long long *>(nullptr));
+                           pin ? h_counts : static_cast<unsigned long long *>(nullptr));
     } else {
         const unsigned hgrid = (unsigned)ctx->num_cus * 2;
         hipLaunchKernelGGL(hits_best_value, dim3(hgrid), dim3(kBlock), 0, st, fo.hits, fo.hit_count, cap, d_bval);
@@ -724,18 +746,17 @@ static int argmax_by_prefilter(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
                            d_bkey);
         hipLaunchKernelGGL(argmax_collect, dim3((unsigned)((npos + 255) / 256)), dim3(256), 0, st, (unsigned)npos,
                            d_bval, d_bkey, res, fo.hit_count,
-                           pin ? static_cast<unsigned long long *>(ctx->pinned) : static_cast<unsigned long long *>(nullptr));
+                           pin ? h_counts : static_cast<unsigned long long *>(nullptr));
     }
     LM_HIP_TRY(hipGetLastError());
     std::vector<ArgmaxRecord> host_res(pin ? 0 : npos);
     if (!pin) {
-        LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, base, 16, hipMemcpyDeviceToHost, st));
+        LM_HIP_TRY(hipMemcpyAsync(h_counts, base, 16, hipMemcpyDeviceToHost, st));
         LM_HIP_TRY(hipMemcpyAsync(host_res.data(), d_res, npos * sizeof(ArgmaxRecord), hipMemcpyDeviceToHost, st));
     }
     LM_HIP_TRY(hipStreamSynchronize(st));
     scan_timer_read(ctx);
-    const unsigned long long nhits = static_cast<unsigned long long *>(ctx->pinned)[0];
-    const unsigned long long ncand = static_cast<unsigned long long *>(ctx->pinned)[1];
+    const unsigned long long nhits = h_counts[0], ncand = h_counts[1];
     if (getenv("LM_HIP_TRACE"))
         fprintf(stderr, "[lm_hip] candidate-route argmax: %zu jobs, %llu candidates (room %llu), %llu hits (room %llu)\n",
                 npos, ncand, ccap, nhits, cap);

@@ -343,8 +343,7 @@ int reserve_hit_lists(lm_hip_ctx *ctx, size_t head_bytes, unsigned long long cap
 
 int upload_head(lm_hip_ctx *ctx, hipStream_t st, char *base, size_t head_bytes, size_t zero_bytes, const HeadPart *parts, size_t nparts)
 {
-    if (head_bytes <= kPinnedBytes / 2) {
-        char *head = static_cast<char *>(ctx->pinned) + kPinnedBytes / 2;
+    if (char *head = pinned_at<char>(ctx, kPinUploadHead, head_bytes)) {
         memset(head, 0, zero_bytes);
         for (size_t i = 0; i < nparts; ++i)
             if (parts[i].src)

@@ -285,10 +285,10 @@ static int order_or_grow(lm_hip_ctx *ctx, bool speculate, const FusedOut &fo, co
             return LM_HIP_OK;
         }
     } else {
-        LM_HIP_TRY(hipMemcpyAsync(ctx->pinned, base, 16, hipMemcpyDeviceToHost, ctx->stream));
-        LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        count = static_cast<unsigned long long *>(ctx->pinned)[0];
-        ncand = static_cast<unsigned long long *>(ctx->pinned)[1];
+        unsigned long long counts[2];
+        LM_TRY(read_back_counters(ctx, ctx->stream, base, counts));
+        count = counts[0];
+        ncand = counts[1];
         if (ncand > ccap) {
             // the hit count of a truncated candidate list means nothing yet
             ctx->last_cand_count = ncand;
