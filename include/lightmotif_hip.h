@@ -84,6 +84,13 @@ typedef struct lm_hip_set_hit {
     float score;
 } lm_hip_set_hit;
 
+/* The best window of one motif in one record of a sequence set (lm_hip_scan_best_seqset): 16 bytes. */
+typedef struct lm_hip_set_best {
+    uint64_t position; /* inside the record; 0 when found == 0 */
+    float score;       /* NaN when found == 0 */
+    int32_t found;
+} lm_hip_set_best;
+
 typedef struct lm_hip_ctx lm_hip_ctx;       /* device + stream + scratch */
 typedef struct lm_hip_pssm lm_hip_pssm;     /* ScoringMatrix data resident on the device */
 typedef struct lm_hip_seq lm_hip_seq;       /* StripedSequence resident on the device */
@@ -394,6 +401,34 @@ int lm_hip_seqset_destroy(lm_hip_seqset *set);
  * matrix's alphabet size differs from the set's.  A motif longer than every record has no hits. */
 int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds,
                                  size_t n, const lm_hip_seqset *set, size_t *counts, lm_hip_set_hit **hits);
+
+/* The dense motifs x records matrix of best windows: what the reference's README asks of one sequence
+ * (`pssm.score(&striped).argmax()`, scores.rs:190-192) and its CLI would ask once per (motif, record) job
+ * (main.rs:502-561), for every motif and every record of the set in ONE call, without a score matrix or a hit list.
+ * best[i * records + r] (motif-major, caller's memory, n * records entries) describes motif i (M rows) in record r
+ * (L_r symbols).  The windows are the positions p = 0 .. L_r - M, all inside the record (scan.rs:185-190, per RECORD);
+ * each scores as score_into scores it, M sequential f32 adds from +0.0 in row order (pli/mod.rs:96-105), bit for bit
+ * the score it has when the record is striped alone.
+ *   found = 0   the record has no window (L_r < M, empty records included) or every window scores NaN;
+ *               then position = 0 and score = NaN
+ *   found = 1   score = the greatest window score under f32 `>` (NaN windows never compete, -inf windows do: a record
+ *               of only -inf windows answers (-inf, 0)), position = the LOWEST record-relative position holding it
+ * i.e. among record r's hits in lm_hip_scan_threshold_seqset's list for a threshold of -inf, the greatest score and
+ * the first of those in list order.  Deterministic, identical from call to call and with the prefilter on or off: the
+ * route is exact f32 throughout (csrc/seqset_best.hip; lm_hip_ctx_last_kernel names the kernel that ran last,
+ * `seqset_best_fused<M>` up to M = 36, `seqset_best_generic` beyond).
+ * This deliberately is NOT Maximum::argmax (pli/mod.rs:135-155) on the record's own score matrix: that rule also scans
+ * the cells of the padded tail and takes the LAST maximal cell in (row, col) order.  The two agree -- same score, and
+ * position = col * rows + row of the record striped alone -- when the maximum over the valid windows is unique and the
+ * default symbol's column of the matrix is -inf (no padded cell can then reach it).
+ * LM_HIP_ERR_WRAP when the set's wrap < max(M) - 1; LM_HIP_ERR_BAD_ARGS, before any launch, on null arguments or a
+ * matrix whose alphabet size differs from the set's; LM_HIP_OK with nothing written when n == 0 or the set has no
+ * records; LM_HIP_ERR_OOM when the device cannot hold the result block of one motif (motifs are scanned in groups that
+ * bound the block at 256 MB).  The merge packs record-relative positions into 32 bits: a set with a record of 2^32 or
+ * more symbols is refused with LM_HIP_ERR_CAPACITY before any launch; offsets and global positions are 64-bit
+ * throughout. */
+int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set,
+                            lm_hip_set_best *best);
 
 /* Scanner (scan.rs:96-250), collected: every position with score >= threshold and
  * position + M <= L (scan.rs:185-190), as (position, f32 score) sorted by position

@@ -27,6 +27,10 @@ class SetHit(C.Structure):
     _fields_ = [("record", C.c_size_t), ("position", C.c_size_t), ("score", C.c_float)]
 
 
+class SetBest(C.Structure):
+    _fields_ = [("position", C.c_uint64), ("score", C.c_float), ("found", C.c_int32)]
+
+
 class LightmotifHipError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"lightmotif_hip error {status}: {message}")
@@ -107,6 +111,7 @@ SIGNATURES = {
     "lm_hip_seqset_lengths": (C.c_int, [_vp, _vp, _sz]),
     "lm_hip_seqset_destroy": (C.c_int, [_vp]),
     "lm_hip_scan_threshold_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _szp, C.POINTER(C.POINTER(SetHit))]),
+    "lm_hip_scan_best_seqset": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, C.POINTER(SetBest)]),
     "lm_hip_scan_f32": (C.c_int, [_vp, _vp, _vp, C.c_float, C.POINTER(C.POINTER(Hit)), _szp]),
     "lm_hip_scan_max_f32": (C.c_int, [_vp, _vp, _vp, _vp, _sz, C.c_int, C.c_uint, C.c_int, _sz, C.c_float, _sz, _ip,
                                       C.POINTER(Hit)]),

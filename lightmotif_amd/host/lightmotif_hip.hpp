@@ -1352,6 +1352,31 @@ public:
         lm_hip_free(h);
         return out;
     }
+    // The best window of every motif in every record of a set in one call (lm_hip_scan_best_seqset): out[i][r] for motif
+    // i and record r -- the greatest score over the windows position + M <= len(record) (scan.rs:185-190) at the LOWEST
+    // position holding it; found = false (position 0, score NaN) when the record has no window or every window is NaN.
+    // Not Maximum::argmax of the record's own matrix (pli/mod.rs:135-155), which also scans the padded tail.
+    struct SetBest {
+        bool found;
+        size_t position;
+        float score;
+    };
+    std::vector<std::vector<SetBest>> scan_best(const std::vector<const ScoringMatrix<A> *> &pssms, const SequenceSet<A> &set) const
+    {
+        const size_t n = pssms.size(), records = set.records();
+        std::vector<const lm_hip_pssm *> handles(n);
+        for (size_t i = 0; i < n; ++i)
+            handles[i] = pssms[i]->device(ctx_->ctx);
+        std::vector<lm_hip_set_best> flat(n * records);
+        check(lm_hip_scan_best_seqset(ctx_->ctx, handles.data(), n, set.handle(), flat.data()));
+        std::vector<std::vector<SetBest>> out(n, std::vector<SetBest>(records));
+        for (size_t i = 0; i < n; ++i)
+            for (size_t r = 0; r < records; ++r) {
+                const lm_hip_set_best &b = flat[i * records + r];
+                out[i][r] = {b.found != 0, (size_t)b.position, b.score};
+            }
+        return out;
+    }
 
     // ---- row-sharded jobs across the GPUs of a node -----------------------------------
     // Score::score_rows_into takes a row range so that a sequence can be cut (pli/mod.rs:72-78):

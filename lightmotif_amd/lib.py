@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "CountMatrix", "WeightMatrix",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -322,6 +322,19 @@ class Pipeline:
         total = int(counts.sum())
         raw = self._take_array(ptr, total * C.sizeof(SetHit), np.uint8)
         return SetHits(raw.view(SET_HIT_DTYPE) if total else np.zeros(0, dtype=SET_HIT_DTYPE), counts)
+
+    def scan_best_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], seqset: "StripedSequenceSet") -> "SetBest":
+        """The dense ``motifs x records`` matrix of best windows in one call (``lm_hip_scan_best_seqset``): per (motif,
+        record) the greatest score over the windows ``position + M <= len(record)`` (scan.rs:185-190) and the LOWEST
+        position holding it; NaN windows never compete.  No score matrix and no hit list exist on the way."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms)
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        n, records = len(batch), len(seqset)
+        raw = np.zeros(n * records, dtype=SET_BEST_DTYPE)
+        check(self._L.lm_hip_scan_best_seqset(self._h, batch.handles, n, seqset._h,
+                                              raw.ctypes.data_as(C.POINTER(_ffi.SetBest)) if raw.size else None))
+        return SetBest(raw.reshape(n, records), self.last_kernel if raw.size else "")
 
     def upload(self, data: np.ndarray, length: int, wrap: int, columns: int,
                protein: bool = False) -> "StripedSequence":
@@ -1159,6 +1172,30 @@ class SetHits(Sequence):
     @property
     def total(self) -> int:
         return int(self._starts[-1])
+
+
+SET_BEST_DTYPE = np.dtype({"names": ["position", "score", "found"], "formats": [np.uint64, np.float32, np.int32],
+                           "offsets": [0, 8, 12], "itemsize": C.sizeof(_ffi.SetBest)})   # lm_hip_set_best
+
+
+class SetBest:
+    """The result of ``Pipeline.scan_best_set``: three ``(motifs, records)`` arrays -- ``found`` (bool), ``position``
+    (int64, -1 where not found) and ``score`` (float32, NaN where not found); ``last_kernel`` names the kernel that ran
+    last for the call ("" when nothing ran)."""
+
+    def __init__(self, raw: np.ndarray, last_kernel: str = ""):
+        self.raw = raw                                   # (motifs, records) of lm_hip_set_best
+        self.found = raw["found"] != 0
+        self.position = np.where(self.found, raw["position"].astype(np.int64), np.int64(-1))
+        self.score = np.where(self.found, raw["score"], np.float32(np.nan)).astype(np.float32)
+        self.last_kernel = last_kernel
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return self.raw.shape
+
+    def __len__(self) -> int:
+        return self.raw.shape[0]
 
 
 # --- scores -----------------------------------------------------------------------------

@@ -16,6 +16,9 @@ Behaviour follows lightmotif-cli/src/main.rs:
     1-based indices and the p-value in exponent notation (main.rs:527-531, 587-600).
     The reference writes hits in worker-completion order; this driver writes them grouped by
     sequence, then strand, then motif, then position.
+``--best`` writes, instead of the hits above a threshold, ONE line per (sequence, strand, motif) that has a window: the
+best window of the motif in that record, the lowest position among equal scores (``Pipeline.scan_best_set``); thresholds
+play no part.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -122,6 +125,15 @@ def scan_set(pli: Pipeline, seqset: StripedSequenceSet, batch: MotifBatch):
     return motif[order], pos[order], score[order], bounds
 
 
+def best_set(pli: Pipeline, seqset: StripedSequenceSet, batch: MotifBatch):
+    """The best window of every motif in every record of a set, in the form of ``scan_set``: one entry per (record, motif)
+    that has a window, ordered by record, then motif."""
+    res = pli.scan_best_set(batch, seqset)
+    rec, motif = np.nonzero(res.found.T)           # row-major over (record, motif): the order of the table
+    bounds = np.searchsorted(rec, np.arange(len(seqset) + 1))
+    return motif.astype(np.int64), res.position[motif, rec], res.score[motif, rec], bounds
+
+
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
@@ -132,6 +144,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     group.add_argument("--abs-threshold", type=float)
     group.add_argument("--rel-threshold", type=float)
     ap.add_argument("--reverse", action="store_true", help="also scan the reverse-complement matrices")
+    ap.add_argument("--best", action="store_true",
+                    help="write the best window of every motif in every record instead of the hits above a threshold")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch-bases", type=int, default=DEFAULT_BATCH_BASES,
                     help="bases of sequence gathered into one resident set and scanned with one call per strand "
@@ -162,7 +176,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         def flush(first_index: int, names: List[str], texts: List[str]) -> int:
             seqset = pli.stripe_ascii_set(texts, lossy=True)
             seqset.configure_wrap(max_m)                                   # main.rs:543
-            found = [(strand, scan_set(pli, seqset, batch)) for strand, batch in batches]
+            found = [(strand, (best_set if args.best else scan_set)(pli, seqset, batch)) for strand, batch in batches]
             wrote = 0
             for r, name in enumerate(names):
                 for strand, (motif, pos, score, bounds) in found:

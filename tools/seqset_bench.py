@@ -13,6 +13,14 @@ Cases: (i) 2 000 records x 500 bp x 64 JASPAR motifs, (ii) 50 000 records x 200 
 tests/golden/JASPAR2024.pwm.gz; thresholds at p = 1e-5.  Reports median and spread (min, max) of every way, the ratios
 A/B and B/C, the share of call C that its tail takes (re-score + order + host, ``lm_hip_ctx_last_phases_ms``), and the
 sustained shader clock.  ``python tools/seqset_bench.py [--case i|ii|both] [--runs 7] [--out profiles/seqset_bench.json]``
+
+``--best`` measures the best-hit-per-record matrix instead (``measure_best``; 2 000 records x 500 bp x 8 motifs, the set
+resident, the calls alone timed) and writes ``profiles/seqset_best_bench.json``:
+
+  A'  ``scan_threshold_set`` at thresholds of -inf + the reduction per (motif, record) in numpy: the cheapest single
+      call that gave the answer before ``scan_best_set`` existed (a 16-byte hit for every window of every motif);
+  B'  ``scan_best_set``;
+  C'  ``scan_argmax_batch`` over the plain concatenation: the bare fused argmax, no segmentation -- not the answer.
 """
 from __future__ import annotations
 
@@ -135,6 +143,92 @@ def measure(pli, n_records, length, n_motifs, runs=7, warmup=2, with_loop=True, 
     return out
 
 
+def reduce_hits(res, n_records):
+    """A': (found, position, score) of shape (motifs, records) from a ``SetHits`` that holds every window: per record the
+    greatest score and the first position holding it (the lists are ascending in (record, position))."""
+    n = len(res)
+    found = np.zeros((n, n_records), dtype=bool)
+    position = np.full((n, n_records), -1, dtype=np.int64)
+    score = np.full((n, n_records), np.nan, dtype=np.float32)
+    for mi in range(n):
+        rec, pos, val = res[mi]
+        keep = ~np.isnan(val)                     # NaN windows never compete
+        rec, pos, val = rec[keep], pos[keep], val[keep]
+        if not len(rec):
+            continue
+        starts = np.flatnonzero(np.concatenate(([True], rec[1:] != rec[:-1])))
+        best = np.maximum.reduceat(val, starts)
+        seg = np.cumsum(np.concatenate(([0], (rec[1:] != rec[:-1]).astype(np.int64))))
+        at = np.flatnonzero(val == best[seg])     # ascending: the first of a record is its lowest position
+        first = at[np.concatenate(([True], rec[at][1:] != rec[at][:-1]))]
+        found[mi, rec[first]] = True
+        position[mi, rec[first]] = pos[first]
+        score[mi, rec[first]] = val[first]
+    return found, position, score
+
+
+def measure_best(pli, n_records, length, n_motifs, runs=5, warmup=1):
+    """A', B', C' (module docstring) on one resident set, alternating, medians of `runs` after `warmup`; the answers of A'
+    and B' are compared first."""
+    pssms, _ = load_motifs(n_motifs)
+    lengths = [len(p) for p in pssms]
+    max_m = max(lengths)
+    _, joined = make_records(n_records, length)
+    offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(length)
+    seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+    seqset.configure_wrap(max_m)
+    plain = pli.stripe_ascii(joined, lossy=True)
+    plain.configure_wrap(max_m)
+    dense = pli.prepare_batch(pssms, [-np.inf] * len(pssms))
+    batch = pli.prepare_batch(pssms)
+
+    kernels = set()
+
+    def way_a():
+        res = pli.scan_threshold_set(dense, None, seqset)
+        return res.total, reduce_hits(res, n_records)
+
+    def way_b():
+        res = pli.scan_best_set(batch, seqset)
+        kernels.add(res.last_kernel)
+        return res.found.size, (res.found, res.position, res.score)
+
+    def way_c():
+        return len(pli.scan_argmax_batch(pssms, plain)), None
+
+    (hits_a, a), (_, b) = way_a(), way_b()
+    same = bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1]) and
+                np.array_equal(a[2].view(np.uint32), b[2].view(np.uint32)))
+    ways = {"A": way_a, "B": way_b, "C": way_c}
+    times = {k: [] for k in ways}
+    for it in range(warmup + runs):
+        for k in sorted(ways):
+            if k == "A":
+                ways[k]()                         # steady state, as in measure(): the hit list is sized from the call before
+            t0 = time.perf_counter()
+            ways[k]()
+            if it >= warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    out = {"records": n_records, "record_length": length, "motifs": len(pssms), "motif_lengths": lengths, "runs": runs,
+           "warmup": warmup, "answers_equal": same, "windows": int(hits_a), "found": int(b[0].sum()), "kernel": sorted(kernels),
+           "ms": {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "all": [round(x, 3) for x in v]}
+                  for k, v in times.items()}}
+    out["A_over_B"] = out["ms"]["A"]["median"] / out["ms"]["B"]["median"]
+    out["B_over_C"] = out["ms"]["B"]["median"] / out["ms"]["C"]["median"]
+    return out
+
+
+def main_best(a):
+    pli = lm.Pipeline.hip(0)
+    res = measure_best(pli, 2_000, 500, 8, runs=a.runs, warmup=2)
+    out = a.out if a.out != str(ROOT / "profiles" / "seqset_bench.json") else str(ROOT / "profiles" / "seqset_best_bench.json")
+    result = {"tool": "tools/seqset_bench.py --best", "device": "MI355X (gfx950)", "case": res}
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps({"A_over_B": res["A_over_B"], "B_over_C": res["B_over_C"], "answers_equal": res["answers_equal"], "wrote": out}))
+    return 0 if res["answers_equal"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="both", choices=["i", "ii", "both"])
@@ -142,7 +236,10 @@ def main():
     ap.add_argument("--runs-ii", dest="loop_runs_ii", type=int, default=5, help="runs of case (ii)")
     ap.add_argument("--loop-records-ii", type=int, default=500, help="records the loop of case (ii) runs over (scaled to 50 000)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "seqset_bench.json"))
+    ap.add_argument("--best", action="store_true", help="the best hit per record (measure_best) -> profiles/seqset_best_bench.json")
     a = ap.parse_args()
+    if a.best:
+        return main_best(a)
     pli = lm.Pipeline.hip(0)
     result = {"tool": "tools/seqset_bench.py", "device": "MI355X (gfx950)", "cases": {}}
     for name in (["i", "ii"] if a.case == "both" else [a.case]):
