@@ -390,6 +390,36 @@ int lm_hip_seqset_record_length(const lm_hip_seqset *set, size_t record, size_t 
 int lm_hip_seqset_lengths(const lm_hip_seqset *set, size_t *lengths, size_t capacity);
 int lm_hip_seqset_destroy(lm_hip_seqset *set);
 
+/* A set straight from the bytes of a FASTA file: the reference CLI's compiled reader in front of encode_lossy
+ * (main.rs:532-546, seq.rs:122-129), with the container parsed ON THE DEVICE (csrc/fasta.hip) -- the host uploads the
+ * raw bytes and never looks at a sequence line.  The grammar, on bytes: lines end at '\n' (the last need not have one); a
+ * line whose first byte is '>' is a header line and starts a record; every other line is a sequence line of the record
+ * opened by the nearest header line before it, and sequence lines before the first header are dropped; in sequence lines
+ * the bytes 0x09-0x0D and 0x20 are dropped wherever they stand and every other byte is a residue that goes through the
+ * table of lm_hip_seq_from_ascii (a '>' in mid-line is an invalid residue); records may be empty, and input without a
+ * header line is a set of zero records.  For plain FASTA (ASCII, "\n" or "\r\n" line ends, whitespace only at the ends of
+ * a sequence line) these are the records a line-by-line text reader yields; they differ on whitespace inside a sequence
+ * line (dropped here), on a lone '\r' (no line end here) and on non-ASCII bytes (invalid residues here).
+ *   out        an ordinary lm_hip_seqset: matrix and offsets equal, byte for byte, what lm_hip_seqset_from_ascii
+ *              builds from the parsed records
+ *   headers    may be NULL; otherwise *headers receives *n_records spans (NULL when there are none; release with
+ *              lm_hip_free): bytes [begin, end) of `text` = one header line without its '>' and without its '\n' (a
+ *              '\r' in front of the '\n' stays inside the span)
+ *   bad_record / bad_index   strict mode, LM_HIP_ERR_INVALID_SYMBOL: the first offending residue (the smallest position
+ *              of the concatenation) as (record, index inside the record), as lm_hip_seqset_from_ascii; either may be NULL
+ * LM_HIP_ERR_BAD_ARGS, before any device work, for a null ctx / out / n_records, a null text with nbytes > 0, cols == 0 or
+ * an alphabet other than 'D' / 'P'; LM_HIP_ERR_CAPACITY when the residues exceed the 2^40 cells a hit list addresses;
+ * LM_HIP_ERR_OOM as lm_hip_seqset_from_ascii.  On any failure *out is NULL.  Device memory peaks below 3 x nbytes (raw
+ * text, compact text, matrix); the first two are released before the call returns.  Every position and count is 64-bit;
+ * results are identical from call to call.  Synchronises. */
+typedef struct { uint64_t begin, end; } lm_hip_fasta_span;   /* bytes [begin, end) of the input */
+int lm_hip_seqset_from_fasta(lm_hip_ctx *ctx, char alphabet, const uint8_t *text, size_t nbytes,
+                             size_t cols, int lossy, lm_hip_seqset **out,
+                             lm_hip_fasta_span **headers, size_t *n_records,
+                             size_t *bad_record, size_t *bad_index);
+/* Bytes of input one workgroup parses (the tile of csrc/fasta.hip); needs no device. */
+size_t lm_hip_fasta_tile_bytes(void);
+
 /* `n` motifs x every record of the set in ONE call (main.rs:502-561 collapsed): per motif, in caller order, every
  * (record, position) with score >= threshold and position + M <= len(record) (scan.rs:185-190, per RECORD), sorted by
  * record, then position.  counts[i] hits for motif i; *hits holds sum(counts) entries (release with lm_hip_free; NULL

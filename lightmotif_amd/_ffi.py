@@ -105,6 +105,8 @@ SIGNATURES = {
                                               C.POINTER(_cp), C.POINTER(_fp)]),
     "lm_hip_seqset_from_ascii": (C.c_int, [_vp, C.c_char, _vp, _sz, _vp, _sz, _sz, C.c_int, C.POINTER(_vp), _szp, _szp]),
     "lm_hip_seqset_from_encoded": (C.c_int, [_vp, _vp, _sz, _vp, _sz, _sz, _sz, C.POINTER(_vp)]),
+    "lm_hip_seqset_from_fasta": (C.c_int, [_vp, C.c_char, _vp, _sz, _sz, C.c_int, C.POINTER(_vp), C.POINTER(_vp), _szp, _szp, _szp]),
+    "lm_hip_fasta_tile_bytes": (_sz, []),
     "lm_hip_seqset_configure_wrap": (C.c_int, [_vp, _vp, _sz]),
     "lm_hip_seqset_info": (C.c_int, [_vp, _szp, _szp, _szp, _szp, _szp, _szp]),
     "lm_hip_seqset_record_length": (C.c_int, [_vp, _sz, _szp]),

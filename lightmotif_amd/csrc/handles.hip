@@ -59,8 +59,10 @@ static int check_symbols(lm_hip_ctx *ctx, const uint8_t *d_data, size_t rows, si
     return LM_HIP_OK;
 }
 
-static int seq_alloc(lm_hip_ctx *ctx, size_t rows, size_t stride, size_t cols, size_t length,
-                     size_t k, lm_hip_seq **out, size_t min_capacity_rows = 0)
+}  // extern "C"
+
+int lm::seq_alloc(lm_hip_ctx *ctx, size_t rows, size_t stride, size_t cols, size_t length,
+                  size_t k, lm_hip_seq **out, size_t min_capacity_rows)
 {
     lm_hip_seq *s = new (std::nothrow) lm_hip_seq();
     if (!s)
@@ -80,6 +82,8 @@ static int seq_alloc(lm_hip_ctx *ctx, size_t rows, size_t stride, size_t cols, s
     *out = s;
     return LM_HIP_OK;
 }
+
+extern "C" {
 
 int lm_hip_seq_upload(lm_hip_ctx *ctx, const uint8_t *data, size_t rows_total, size_t stride,
                       size_t cols, size_t wrap, size_t length, size_t k, lm_hip_seq **out)
@@ -140,6 +144,8 @@ int lm_hip_seq_adopt_dptr(lm_hip_ctx *ctx, uint8_t *d_data, size_t rows_total, s
     return LM_HIP_OK;
 }
 
+}  // extern "C"
+
 // ---- host sequence -> resident StripedSequence (Encode + Stripe, pli/mod.rs:56-66, 178-200) ------------
 //
 // The caller's buffer (ASCII text or symbol bytes, pageable) goes to the device TILE by tile: tile t = rows
@@ -149,7 +155,7 @@ int lm_hip_seq_adopt_dptr(lm_hip_ctx *ctx, uint8_t *d_data, size_t rows_total, s
 // whatever the genome's size, nothing is staged twice, and the H2D transfer -- the floor of this step: a
 // pageable 1 GB buffer moves at ~55 GB/s on this host, 18 ms -- hides the 0.8 ms/Gbp of kernels behind it.
 // (Round 2 copied the whole text into a 2 x len scratch with one hipMemcpyAsync, then encoded, then striped.)
-static int ingest_streams(lm_hip_ctx *ctx)
+int lm::ingest_streams(lm_hip_ctx *ctx)
 {
     if (ctx->copy_stream)
         return LM_HIP_OK;
@@ -175,6 +181,8 @@ static int ingest_streams(lm_hip_ctx *ctx)
     ctx->copy_stream = st;
     return LM_HIP_OK;
 }
+
+extern "C" {
 
 constexpr size_t kIngestTileBytes = 32u << 20;
 

@@ -626,4 +626,13 @@ int launch_n_runs(lm_hip_ctx *ctx, const unsigned long long *d_runs, size_t nrun
 int launch_wrap(lm_hip_ctx *ctx, uint8_t *d_data, size_t rows, size_t stride, size_t cols,
                 size_t new_wrap, uint8_t default_symbol);
 
+// handles.hip: a fresh lm_hip_seq with room for `rows` rows + DEFAULT_EXTRA_ROWS (no wrap yet), and the copy stream and
+// events of the host -> device ingest, made on first use.  seqset.hip: a set around a striped sequence whose offsets are
+// on the device already (fasta.hip); takes `seq` and `d_offsets` over, also when it fails.
+int seq_alloc(lm_hip_ctx *ctx, size_t rows, size_t stride, size_t cols, size_t length, size_t k, lm_hip_seq **out,
+              size_t min_capacity_rows = 0);
+int ingest_streams(lm_hip_ctx *ctx);
+int seqset_adopt(lm_hip_ctx *ctx, lm_hip_seq *seq, std::vector<uint64_t> &&offsets, unsigned long long *d_offsets,
+                 lm_hip_seqset **out);
+
 }  // namespace lm

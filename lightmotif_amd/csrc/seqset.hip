@@ -267,6 +267,26 @@ static int seqset_wrap(lm_hip_ctx *ctx, lm_hip_seq *seq, const uint64_t *offsets
     return LM_HIP_OK;
 }
 
+int lm::seqset_adopt(lm_hip_ctx *ctx, lm_hip_seq *seq, std::vector<uint64_t> &&offsets, unsigned long long *d_offsets,
+                     lm_hip_seqset **out)
+{
+    lm_hip_seqset *s = new (std::nothrow) lm_hip_seqset();
+    if (!s) {
+        {
+            DeviceGuard guard(ctx->device);
+            (void)hipFree(d_offsets);
+        }
+        lm_hip_seq_destroy(seq);
+        return fail(LM_HIP_ERR_OOM, "out of host memory");
+    }
+    s->device = ctx->device;
+    s->seq = seq;
+    s->offsets = std::move(offsets);
+    s->d_offsets = d_offsets;
+    *out = s;
+    return LM_HIP_OK;
+}
+
 extern "C" {
 
 int lm_hip_seqset_from_ascii(lm_hip_ctx *ctx, char alphabet, const uint8_t *text, size_t total, const uint64_t *offsets,

@@ -42,6 +42,14 @@ struct UnsupportedBackend : std::runtime_error {  // err.rs:34
 struct InvalidSymbol : std::invalid_argument {  // err.rs:10
     char symbol;
     explicit InvalidSymbol(char c) : std::invalid_argument(std::string("invalid symbol: ") + c), symbol(c) {}
+    // ... met by the device's FASTA reader: the residue's place, (record, index inside the record).  The byte itself is not
+    // reported on this road: `symbol` is 0 (NUL) there, so a handler that prints it should print record / index instead
+    size_t record = 0, index = 0;
+    InvalidSymbol(size_t r, size_t i)
+        : std::invalid_argument("invalid symbol at position " + std::to_string(i) + " of record " + std::to_string(r)), symbol(0),
+          record(r), index(i)
+    {
+    }
 };
 struct InvalidData : std::invalid_argument {  // err.rs:22
     InvalidData() : std::invalid_argument("invalid data") {}
@@ -191,10 +199,21 @@ private:
 template <class A>
 class SequenceSet {
 public:
-    SequenceSet(std::shared_ptr<CtxHandle> c, lm_hip_seqset *h) : ctx_(std::move(c)), h_(h) {}
+    SequenceSet(std::shared_ptr<CtxHandle> c, lm_hip_seqset *h, std::vector<lm_hip_fasta_span> spans = {})
+        : ctx_(std::move(c)), h_(h), spans_(std::move(spans))
+    {
+    }
     ~SequenceSet() { lm_hip_seqset_destroy(h_); }
-    SequenceSet(SequenceSet &&o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_) { o.h_ = nullptr; }
+    SequenceSet(SequenceSet &&o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_), spans_(std::move(o.spans_)) { o.h_ = nullptr; }
     SequenceSet(const SequenceSet &) = delete;
+
+    // The records of a FASTA file, parsed on the device from its bytes (lm_hip_seqset_from_fasta, where the grammar is
+    // stated; main.rs:532-546): the host uploads `size` bytes and never looks at a sequence line.  Strict mode throws
+    // InvalidSymbol(record, index) for the first residue outside the alphabet.
+    static SequenceSet from_fasta(const Pipeline<A> &pipeline, const void *data, size_t size, bool lossy = false, size_t columns = 32);
+    // ... per record the bytes [begin, end) of the input that hold its header line, without the '>' and the '\n' (empty for
+    // sets made otherwise)
+    const std::vector<lm_hip_fasta_span> &header_spans() const { return spans_; }
 
     size_t records() const { return info().records; }
     size_t total_length() const { return info().total; }
@@ -228,6 +247,7 @@ private:
     }
     std::shared_ptr<CtxHandle> ctx_;
     lm_hip_seqset *h_;
+    std::vector<lm_hip_fasta_span> spans_;
 };
 
 // ---- matrices (pwm/mod.rs) ---------------------------------------------------------------------
@@ -1310,6 +1330,21 @@ public:
         check(st);
         return SequenceSet<A>(ctx_, h);
     }
+    // ... from the bytes of a FASTA file, parsed on the device (lm_hip_seqset_from_fasta): SequenceSet::from_fasta
+    SequenceSet<A> stripe_fasta_set(const void *data, size_t size, bool lossy = false, size_t columns = 32) const
+    {
+        lm_hip_seqset *h = nullptr;
+        lm_hip_fasta_span *raw = nullptr;
+        size_t n = 0, bad_record = 0, bad_index = 0;
+        const int st = lm_hip_seqset_from_fasta(ctx_->ctx, A::code, static_cast<const uint8_t *>(data), size, columns, lossy ? 1 : 0, &h,
+                                                &raw, &n, &bad_record, &bad_index);
+        if (st == LM_HIP_ERR_INVALID_SYMBOL)
+            throw InvalidSymbol(bad_record, bad_index);
+        check(st);
+        std::vector<lm_hip_fasta_span> spans(raw, raw + (raw ? n : 0));
+        lm_hip_free(raw);
+        return SequenceSet<A>(ctx_, h, std::move(spans));
+    }
     // ... from encoded records (lm_hip_seqset_from_encoded)
     SequenceSet<A> stripe_set(const std::vector<EncodedSequence<A>> &records, size_t columns = 32) const
     {
@@ -1408,6 +1443,12 @@ private:
     explicit Pipeline(std::shared_ptr<CtxHandle> c) : ctx_(std::move(c)) {}
     std::shared_ptr<CtxHandle> ctx_;
 };
+
+template <class A>
+SequenceSet<A> SequenceSet<A>::from_fasta(const Pipeline<A> &pipeline, const void *data, size_t size, bool lossy, size_t columns)
+{
+    return pipeline.stripe_fasta_set(data, size, lossy, columns);
+}
 
 // The merge rule on host arrays (any transport): per-shard results in ascending row order, rows
 // global, first-cell rule applied on the shard holding row 0 only -> Maximum::argmax of the whole

@@ -25,7 +25,7 @@ from . import _ffi
 from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, UnsupportedBackend, check
 
 __all__ = [
-    "pack_2bit",
+    "pack_2bit", "fasta_names",
     "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "CountMatrix", "WeightMatrix",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -290,6 +290,28 @@ class Pipeline:
             raise InvalidSymbol(f"Invalid symbol in sequence {bad_r.value} at position {bad_i.value}: {chr(byte)!r}")
         check(st)
         return StripedSequenceSet(self, h, protein)
+
+    def stripe_fasta_set(self, data, protein: bool = False, lossy: bool = False,
+                         columns: int = DEFAULT_COLUMNS) -> "StripedSequenceSet":
+        """The bytes of a FASTA file -> ONE resident striped sequence of its records, parsed on the device
+        (``lm_hip_seqset_from_fasta``; the grammar is stated there): the host uploads ``data`` -- ``bytes``, ``bytearray``,
+        ``memoryview`` or a uint8 array, passed without a copy -- and never looks at a sequence line.  The set equals
+        ``stripe_ascii_set`` of the parsed records and carries ``header_spans``: per record the bytes ``[begin, end)`` of
+        ``data`` that hold its header line (``fasta_names(data, spans)`` gives the names)."""
+        buf = np.ascontiguousarray(data, dtype=np.uint8) if isinstance(data, np.ndarray) else np.frombuffer(data, dtype=np.uint8)
+        h, spans = C.c_void_p(), C.c_void_p()
+        n, bad_r, bad_i = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        st = self._L.lm_hip_seqset_from_fasta(self._h, b"P" if protein else b"D", buf.ctypes.data if buf.size else None, buf.size,
+                                              columns, int(lossy), C.byref(h), C.byref(spans), C.byref(n), C.byref(bad_r),
+                                              C.byref(bad_i))
+        if st == _ffi.ERR_INVALID_SYMBOL:
+            err = InvalidSymbol(f"Invalid symbol in sequence {bad_r.value} at position {bad_i.value}")
+            err.record, err.index = bad_r.value, bad_i.value
+            raise err
+        check(st)
+        out = StripedSequenceSet(self, h, protein)
+        out.header_spans = self._take_array(spans, 2 * n.value, np.uint64).reshape(n.value, 2)
+        return out
 
     def stripe_set(self, encoded: Sequence["EncodedSequence"], columns: int = DEFAULT_COLUMNS) -> "StripedSequenceSet":
         """The same from already encoded records (``lm_hip_seqset_from_encoded``)."""
@@ -763,6 +785,8 @@ class StripedSequence:
 
 class StripedSequenceSet:
     """Many records resident as one striped sequence (``lm_hip_seqset``): ``len()`` = records."""
+
+    header_spans: Optional[np.ndarray] = None    # (n, 2) uint64, sets made by ``Pipeline.stripe_fasta_set`` only
 
     def __init__(self, pli: Pipeline, handle: C.c_void_p, protein: bool):
         self._pli, self._h, self.protein = pli, handle, protein
@@ -1543,6 +1567,18 @@ def create(sequences: Iterable[str], *, protein: bool = False, name: Optional[st
     counts = CountMatrix.from_sequences(encoded, protein=protein)
     pwm = counts.normalize(0.0)
     return Motif(counts, pwm, pwm.log_odds(), name)
+
+
+def fasta_names(data, spans: np.ndarray) -> List[str]:
+    """The record names behind the ``header_spans`` of ``Pipeline.stripe_fasta_set(data)``: the header up to its first
+    whitespace, ``""`` for a bare ``>`` (the rule of ``scan_cli.read_fasta``; the ``\\r`` of a ``\\r\\n`` line end goes with
+    the whitespace)."""
+    view = memoryview(data).cast("B") if not isinstance(data, np.ndarray) else memoryview(np.ascontiguousarray(data, dtype=np.uint8))
+    names = []
+    for begin, end in np.asarray(spans, dtype=np.uint64).reshape(-1, 2).tolist():
+        head = bytes(view[begin:end]).split(None, 1)
+        names.append(head[0].decode("utf-8", "replace") if head else "")
+    return names
 
 
 def pack_2bit(encoded: np.ndarray, runs: bool = False):

@@ -8,6 +8,14 @@ Behaviour follows lightmotif-cli/src/main.rs:
     ``--rel-threshold`` (x max score) or ``--abs-threshold``; default p = 1e-5 (main.rs:479-489);
   * every FASTA record is encoded lossily, striped and given ``max_m`` wrap rows
     (main.rs:540-546) -- here on the device, from the raw text;
+  * the FASTA container itself is parsed on the device as well (``--ingest device``, the default): the file is read in
+    binary, cut at record starts into chunks of at most ``--batch-bases`` BYTES of FASTA text (``fasta_chunks``), and each
+    chunk becomes a resident set through ``Pipeline.stripe_fasta_set`` -- the host never looks at a sequence line.
+    ``--ingest host`` is the line-by-line reader ``read_fasta`` in front of ``Pipeline.stripe_ascii_set``, where
+    ``--batch-bases`` counts bases.  On plain FASTA (ASCII, ``\\n`` or ``\\r\\n`` line ends, whitespace only at the ends of a
+    sequence line) both write the same TSV, wherever the sets are cut.  They differ on whitespace INSIDE a sequence line
+    (dropped on the device; a default symbol on the host), on a lone ``\\r`` used as a line end (no line end on the device;
+    text mode makes it one) and on non-ASCII bytes (invalid residues on the device; a decoding matter on the host);
   * the reference fans (motif, sequence) pairs out to worker threads (main.rs:554-561); here
     records are gathered into sets of up to ``--batch-bases`` bases, each set is resident as one
     striped sequence, and all motifs x all records of a set go to the GPU as ONE call per strand
@@ -27,12 +35,12 @@ from __future__ import annotations
 import argparse
 import gzip
 import sys
-from typing import Iterator, List, Optional, Sequence, TextIO, Tuple
+from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
 
 import numpy as np
 
 from . import io as lmio
-from .lib import MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet
+from .lib import MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet, fasta_names
 
 DEFAULT_BATCH_BASES = 100_000_000
 
@@ -41,6 +49,55 @@ def _open_text(path: str) -> TextIO:
     with open(path, "rb") as fh:                     # main.rs:424-436: sniff the gzip magic
         magic = fh.read(2)
     return gzip.open(path, "rt") if magic == b"\x1f\x8b" else open(path, "r")
+
+
+def _open_bytes(path: str) -> BinaryIO:
+    with open(path, "rb") as fh:                     # the same sniff, the bytes as they are
+        magic = fh.read(2)
+    return gzip.open(path, "rb") if magic == b"\x1f\x8b" else open(path, "rb")
+
+
+def fasta_chunks(handle: BinaryIO, budget: int) -> Iterator[bytes]:
+    """Cuts the bytes of a FASTA file into consecutive chunks that concatenate to the file.  Every chunk after the first
+    starts at a ``>`` that follows a ``\\n``, i.e. at a record; a chunk holds at most ``budget`` bytes -- unless one record
+    alone is longer, which then stands alone (text in front of the first header goes with the first record).  The cuts are
+    found with ``bytes.find`` / ``rfind`` and depend on the content alone, not on how the handle delivers it."""
+    if budget < 1:
+        raise ValueError("the byte budget of a chunk must be positive")
+    block = max(budget, 1 << 16)
+    buf, eof, first = b"", False, True
+    while True:
+        while not eof and len(buf) <= budget + 1:    # a record start at byte `budget` shows in budget + 1 bytes
+            more = handle.read(block)
+            if more:
+                buf += more
+            else:
+                eof = True
+        if not buf:
+            return
+        if eof and len(buf) <= budget:
+            cut = len(buf)
+        else:
+            i = buf.rfind(b"\n>", 0, budget + 1)      # the last record start the budget reaches
+            if i < 0:                                # none: one record longer than the budget, up to the next start
+                skip = first and buf[:1] != b">"
+                at = 0
+                while True:
+                    i = buf.find(b"\n>", at)
+                    if i >= 0 and skip:
+                        skip, at = False, i + 1
+                        continue
+                    if i >= 0 or eof:
+                        break
+                    at = max(len(buf) - 1, at)
+                    more = handle.read(block)
+                    if more:
+                        buf += more
+                    else:
+                        eof = True
+            cut = i + 1 if i >= 0 else len(buf)
+        yield buf[:cut]
+        buf, first = buf[cut:], False
 
 
 def read_fasta(handle: TextIO) -> Iterator[Tuple[str, str]]:
@@ -149,7 +206,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch-bases", type=int, default=DEFAULT_BATCH_BASES,
                     help="bases of sequence gathered into one resident set and scanned with one call per strand "
-                         "(a longer record is a set of its own)")
+                         "(a longer record is a set of its own); with --ingest device: bytes of FASTA text per set")
+    ap.add_argument("--ingest", choices=("device", "host"), default="device",
+                    help="where the FASTA container is parsed: on the device from the file's bytes (default), or by the "
+                         "line-by-line reader on the host")
     args = ap.parse_args(argv)
 
     print("Loading matrices")
@@ -170,11 +230,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pli = Pipeline.hip(args.device)
     batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
     n_hits = 0
-    with open(args.output, "w") as out, _open_text(args.sequences) as fasta:
+    opener = _open_bytes if args.ingest == "device" else _open_text
+    with open(args.output, "w") as out, opener(args.sequences) as fasta:
         out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue\n")
 
         def flush(first_index: int, names: List[str], texts: List[str]) -> int:
-            seqset = pli.stripe_ascii_set(texts, lossy=True)
+            return write_set(first_index, names, pli.stripe_ascii_set(texts, lossy=True))
+
+        def write_set(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
             seqset.configure_wrap(max_m)                                   # main.rs:543
             found = [(strand, (best_set if args.best else scan_set)(pli, seqset, batch)) for strand, batch in batches]
             wrote = 0
@@ -188,17 +251,26 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     wrote += b - a
             return wrote
 
-        # the rule of batch_records, applied as the records stream in
-        first, names, texts, bases = 0, [], [], 0
-        for name, text in read_fasta(fasta):
-            if bases > 0 and bases + len(text) > args.batch_bases:
+        if args.ingest == "device":
+            first = 0
+            for chunk in fasta_chunks(fasta, args.batch_bases):
+                seqset = pli.stripe_fasta_set(chunk, lossy=True)
+                names = fasta_names(chunk, seqset.header_spans)
+                if names:
+                    n_hits += write_set(first, names, seqset)
+                first += len(names)
+        else:
+            # the rule of batch_records, applied as the records stream in
+            first, names, texts, bases = 0, [], [], 0
+            for name, text in read_fasta(fasta):
+                if bases > 0 and bases + len(text) > args.batch_bases:
+                    n_hits += flush(first, names, texts)
+                    first, names, texts, bases = first + len(names), [], [], 0
+                names.append(name)
+                texts.append(text)
+                bases += len(text)
+            if names:
                 n_hits += flush(first, names, texts)
-                first, names, texts, bases = first + len(names), [], [], 0
-            names.append(name)
-            texts.append(text)
-            bases += len(text)
-        if names:
-            n_hits += flush(first, names, texts)
     print(f"Wrote {n_hits} hits to {args.output}")
     return 0
 
