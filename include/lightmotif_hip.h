@@ -97,6 +97,7 @@ typedef struct lm_hip_seq lm_hip_seq;       /* StripedSequence resident on the d
 typedef struct lm_hip_seqset lm_hip_seqset; /* many records resident as one StripedSequence + their offsets */
 typedef struct lm_hip_scores lm_hip_scores; /* StripedScores<f32> resident on the device */
 typedef struct lm_hip_comm lm_hip_comm;     /* RCCL communicator of a row-sharded job */
+typedef struct lm_hip_dists lm_hip_dists;   /* ScoreDistribution of n matrices resident on the device */
 
 /* ---- library ------------------------------------------------------------ */
 
@@ -459,6 +460,49 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
  * throughout. */
 int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set,
                             lm_hip_set_best *best);
+
+/* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
+ * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the
+ * `pvalue` column (main.rs:335), built and queried on the device (csrc/dist.hip) instead of motif by motif, hit by hit on
+ * the host.  Per matrix: the weights are discretised to 0 .. 1000 per row (dist.rs:133-161; by the host, in f64), the
+ * rows are convolved into the distribution of the discretised score (dist.rs:164-191: per cell the terms
+ * `old[t - s] * bg[a]` are added in symbol order, one f64 multiply and one f64 add each, never fused), and the
+ * survival function is the sequential sum from the top, clamped at 1 (dist.rs:194-213).  Every number equals, bit for
+ * bit, what lightmotif_amd/dist.py computes on the host, and a call repeats byte for byte.
+ *   pssms        n resident matrices; alphabets may be mixed.  A NaN or +inf weight, or a matrix without a finite
+ *                weight, is LM_HIP_ERR_BAD_ARGS before any launch (the reference panics there); -inf weights are the
+ *                symbols a row cannot hold and are skipped (dist.rs:158-161)
+ *   backgrounds  NULL, or n pointers, each NULL or to k_i f32 frequencies (widened to f64 as dist.rs:171 does); NULL
+ *                stands for the uniform background of abc.rs:473-487 (1 / (K - 1), 0 for the default symbol)
+ *   n == 0       a valid, empty object
+ * MEMORY HELD until lm_hip_dists_destroy: 8 * (1000 * sum(M) + n) bytes of device memory for the survival functions
+ * (about 177 MB for the 2 346 matrices of JASPAR 2024) and 40 bytes per matrix; _create holds up to 4 spare tables per
+ * compute unit on top while it runs.  LM_HIP_ERR_OOM when they do not fit.
+ * SYNCHRONISATION: _create, _sf, _scores and _pvalues each enqueue on the context's stream and synchronise it before
+ * they return; _len, _info and _destroy touch no stream. */
+int lm_hip_dists_create(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const float *const *backgrounds,
+                        lm_hip_dists **out);
+size_t lm_hip_dists_len(const lm_hip_dists *dists);
+/* One matrix's parameters: rows M, `scale` and `offset` of the discretisation (dist.rs:154-155; both whole numbers),
+ * min_score / max_score (the lowest index <= sf_len - 2 / the highest index >= 1 with mass, 0 where there is none:
+ * dist.rs:197-213) and sf_len = 1000 M + 1.  Any out pointer may be NULL.  LM_HIP_ERR_BAD_ARGS for motif >= n. */
+int lm_hip_dists_info(const lm_hip_dists *dists, size_t motif, size_t *rows, double *scale, double *offset, int64_t *min_score,
+                      int64_t *max_score, size_t *sf_len);
+/* Copies one survival function (sf_len f64) to dst; LM_HIP_ERR_CAPACITY when `capacity` (in elements) is short. */
+int lm_hip_dists_sf(lm_hip_ctx *ctx, const lm_hip_dists *dists, size_t motif, double *dst, size_t capacity);
+/* ScoreDistribution::score (dist.rs:104-116) of every matrix in one call: pvalues[i] -> scores[i], n of each.  p >= 1
+ * gives unscale(min_score), p <= 0 unscale(max_score); otherwise the reference's binary search of the descending
+ * table with its probe sequence (it decides which index of a run of equal values comes back).  `unscale` is the f32
+ * arithmetic of dist.rs:84-88. */
+int lm_hip_dists_scores(lm_hip_ctx *ctx, const lm_hip_dists *dists, const double *pvalues, float *scores);
+/* ScoreDistribution::pvalue (dist.rs:91-101) of sum(counts) scores in one call: counts[i] consecutive scores belong to
+ * matrix i, each `score_stride_bytes` (>= 4) behind the last -- so `&hits[0].score` with sizeof(lm_hip_set_hit) or
+ * sizeof(lm_hip_hit), or a plain f32 array with a stride of 4, exactly the per-matrix layout the batch and set scans
+ * return.  Writes one f64 per score.  scaled = round((score - M * offset) * scale) (dist.rs:77-81) converted as Rust's
+ * `as i32` does (saturating; NaN gives 0); scaled < min_score gives 1, scaled >= sf_len gives 0, else sf[scaled]. */
+int lm_hip_dists_pvalues(lm_hip_ctx *ctx, const lm_hip_dists *dists, const size_t *counts, const float *scores,
+                         size_t score_stride_bytes, double *pvalues);
+int lm_hip_dists_destroy(lm_hip_dists *dists);
 
 /* Scanner (scan.rs:96-250), collected: every position with score >= threshold and
  * position + M <= L (scan.rs:185-190), as (position, f32 score) sorted by position

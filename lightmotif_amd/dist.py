@@ -50,6 +50,17 @@ class ScoreDistribution:
         self._scale, self._offset, self._rows = float(scale), int(offset), m
         self.sf, self.min_score, self.max_score = sf, min_score, max_score
 
+    @classmethod
+    def from_parts(cls, sf, scale: float, offset: int, rows: int, min_score: int, max_score: int) -> "ScoreDistribution":
+        """A distribution around a survival function computed elsewhere (``Pipeline.score_distributions`` downloads the
+        device's table): the parts are the attributes ``__init__`` leaves behind, and every method answers from them."""
+        self = cls.__new__(cls)
+        self._scale, self._offset, self._rows = float(scale), int(offset), int(rows)
+        self.sf, self.min_score, self.max_score = np.asarray(sf, dtype=np.float64), int(min_score), int(max_score)
+        if self.sf.shape != (self._rows * CDF_RANGE + 1,):
+            raise ValueError("a survival function has rows * 1000 + 1 entries")
+        return self
+
     def scale(self, score: float) -> int:
         """dist.rs:77-81"""
         x = (float(np.float32(score)) - self._rows * self._offset) * self._scale

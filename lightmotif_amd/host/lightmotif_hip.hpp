@@ -359,6 +359,94 @@ private:
     mutable lm_hip_ctx *dev_ctx_ = nullptr;
 };
 
+// The score distributions of many matrices resident on the device (lm_hip_dists; pwm/dist.rs:51-226): built in one
+// call, then `scores` turns one p-value per matrix into thresholds (dist.rs:104-116) and `pvalues` turns scores into
+// p-values (dist.rs:91-101), each in one call for the whole batch.  Holds 8 * (1000 * sum(M) + n) bytes of device memory.
+template <class A>
+class ScoreDistributions {
+public:
+    ScoreDistributions(std::shared_ptr<CtxHandle> c, const std::vector<const ScoringMatrix<A> *> &pssms) : ctx_(std::move(c))
+    {
+        std::vector<const lm_hip_pssm *> handles(pssms.size());
+        std::vector<const float *> backgrounds(pssms.size());
+        for (size_t i = 0; i < pssms.size(); ++i) {
+            if (pssms[i]->background.size() != A::K)
+                throw std::invalid_argument("a background has one frequency per symbol");
+            handles[i] = pssms[i]->device(ctx_->ctx);
+            backgrounds[i] = pssms[i]->background.data();
+        }
+        check(lm_hip_dists_create(ctx_->ctx, handles.data(), pssms.size(), backgrounds.data(), &h_));
+    }
+    ~ScoreDistributions() { lm_hip_dists_destroy(h_); }
+    ScoreDistributions(ScoreDistributions &&o) noexcept : ctx_(std::move(o.ctx_)), h_(o.h_) { o.h_ = nullptr; }
+    ScoreDistributions(const ScoreDistributions &) = delete;
+
+    size_t size() const { return lm_hip_dists_len(h_); }
+    struct Info {
+        size_t rows, sf_len;
+        double scale, offset;
+        int64_t min_score, max_score;
+    };
+    Info info(size_t motif) const
+    {
+        Info i{};
+        check(lm_hip_dists_info(h_, motif, &i.rows, &i.scale, &i.offset, &i.min_score, &i.max_score, &i.sf_len));
+        return i;
+    }
+    // the survival function of one matrix: sf[t] = P(discretised score >= t), 1000 M + 1 entries
+    std::vector<double> sf(size_t motif) const
+    {
+        std::vector<double> out(info(motif).sf_len);
+        check(lm_hip_dists_sf(ctx_->ctx, h_, motif, out.data(), out.size()));
+        return out;
+    }
+    // ScoreDistribution::score of every matrix: one p-value each, or the same for all
+    std::vector<float> scores(const std::vector<double> &pvalues) const
+    {
+        if (pvalues.size() != size())
+            throw std::invalid_argument("one p-value per matrix");
+        std::vector<float> out(size());
+        check(lm_hip_dists_scores(ctx_->ctx, h_, pvalues.data(), out.data()));
+        return out;
+    }
+    std::vector<float> scores(double pvalue) const { return scores(std::vector<double>(size(), pvalue)); }
+    // ScoreDistribution::pvalue of counts[i] consecutive scores for matrix i, `stride_bytes` apart in memory
+    std::vector<double> pvalues(const std::vector<size_t> &counts, const float *first, size_t stride_bytes = sizeof(float)) const
+    {
+        if (counts.size() != size())
+            throw std::invalid_argument("one count per matrix");
+        size_t total = 0;
+        for (const size_t c : counts)
+            total += c;
+        std::vector<double> out(total);
+        check(lm_hip_dists_pvalues(ctx_->ctx, h_, counts.data(), first, stride_bytes, out.data()));
+        return out;
+    }
+    // ... of per-matrix score lists
+    std::vector<std::vector<double>> pvalues(const std::vector<std::vector<float>> &scores) const
+    {
+        std::vector<size_t> counts(scores.size());
+        std::vector<float> flat;
+        for (size_t i = 0; i < scores.size(); ++i) {
+            counts[i] = scores[i].size();
+            flat.insert(flat.end(), scores[i].begin(), scores[i].end());
+        }
+        const std::vector<double> p = pvalues(counts, flat.data());
+        std::vector<std::vector<double>> out(scores.size());
+        size_t at = 0;
+        for (size_t i = 0; i < scores.size(); ++i) {
+            out[i].assign(p.begin() + at, p.begin() + at + counts[i]);
+            at += counts[i];
+        }
+        return out;
+    }
+    lm_hip_dists *handle() const { return h_; }
+
+private:
+    std::shared_ptr<CtxHandle> ctx_;
+    lm_hip_dists *h_ = nullptr;
+};
+
 template <class A>
 class WeightMatrix {  // pwm/mod.rs:450-456
 public:
@@ -1386,6 +1474,11 @@ public:
         }
         lm_hip_free(h);
         return out;
+    }
+    // The score distributions of a motif list, resident on the device (lm_hip_dists_create; pwm/mod.rs:698-705 per matrix)
+    ScoreDistributions<A> score_distributions(const std::vector<const ScoringMatrix<A> *> &pssms) const
+    {
+        return ScoreDistributions<A>(ctx_, pssms);
     }
     // The best window of every motif in every record of a set in one call (lm_hip_scan_best_seqset): out[i][r] for motif
     // i and record r -- the greatest score over the windows position + M <= len(record) (scan.rs:185-190) at the LOWEST

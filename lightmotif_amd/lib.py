@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -357,6 +357,12 @@ class Pipeline:
         check(self._L.lm_hip_scan_best_seqset(self._h, batch.handles, n, seqset._h,
                                               raw.ctypes.data_as(C.POINTER(_ffi.SetBest)) if raw.size else None))
         return SetBest(raw.reshape(n, records), self.last_kernel if raw.size else "")
+
+    def score_distributions(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"]) -> "ScoreDistributions":
+        """The score distributions (pwm/dist.rs:51-226) of a whole motif list, built and kept on the device
+        (``lm_hip_dists_create``): one call instead of one ``ScoringMatrix.score_distribution`` per motif, bit-identical
+        to it.  Holds ``8 * (1000 * sum(M) + n)`` bytes of device memory."""
+        return ScoreDistributions(self, pssms.pssms if isinstance(pssms, MotifBatch) else pssms)
 
     def upload(self, data: np.ndarray, length: int, wrap: int, columns: int,
                protein: bool = False) -> "StripedSequence":
@@ -1220,6 +1226,94 @@ class SetBest:
 
     def __len__(self) -> int:
         return self.raw.shape[0]
+
+
+class ScoreDistributions:
+    """The resident score distributions of ``n`` motifs (``Pipeline.score_distributions``; ``lm_hip_dists``).
+    ``scale``, ``offset`` (float64, whole numbers), ``min_score``, ``max_score`` (int64) and ``rows`` are arrays with one
+    entry per motif, the parameters ``dist.ScoreDistribution`` keeps (dist.rs:133-161, 197-213)."""
+
+    def __init__(self, pli: Pipeline, pssms: Sequence["ScoringMatrix"]):
+        self._pli, self._L = pli, pli._L
+        self.pssms = list(pssms)              # (keeps the matrices, hence their device tables, alive)
+        n = len(self.pssms)
+        for p in self.pssms:
+            if p.background.shape != (p.k,):
+                raise ValueError("a background has one frequency per symbol")
+        handles = (C.c_void_p * n)(*[p._device(pli) for p in self.pssms])
+        bgs = [np.ascontiguousarray(p.background, dtype=np.float32) for p in self.pssms]
+        bg_ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bgs])
+        self._h = C.c_void_p()
+        check(self._L.lm_hip_dists_create(pli._h, handles, n, bg_ptrs, C.byref(self._h)))
+        self.rows = np.zeros(n, dtype=np.int64)
+        self.scale, self.offset = np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+        self.min_score, self.max_score = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        rows, sc, off, lo, hi = C.c_size_t(0), C.c_double(0), C.c_double(0), C.c_int64(0), C.c_int64(0)
+        for i in range(n):
+            check(self._L.lm_hip_dists_info(self._h, i, C.byref(rows), C.byref(sc), C.byref(off), C.byref(lo), C.byref(hi), None))
+            self.rows[i], self.scale[i], self.offset[i] = rows.value, sc.value, off.value
+            self.min_score[i], self.max_score[i] = lo.value, hi.value
+
+    def __del__(self):
+        try:
+            if self._h:
+                self._L.lm_hip_dists_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def __len__(self) -> int:
+        return len(self.pssms)
+
+    def sf(self, i: int) -> np.ndarray:
+        """The survival function of motif ``i``: float64, ``1000 * M + 1`` entries (``lm_hip_dists_sf``)."""
+        n = len(self)
+        j = i + n if i < 0 else i
+        if not 0 <= j < n:
+            raise IndexError(i)
+        out = np.empty(int(self.rows[j]) * 1000 + 1, dtype=np.float64)
+        check(self._L.lm_hip_dists_sf(self._pli._h, self._h, j, out.ctypes.data, out.size))
+        return out
+
+    def distribution(self, i: int):
+        """Motif ``i``'s distribution as a ``dist.ScoreDistribution`` around the downloaded table."""
+        from .dist import ScoreDistribution
+        n = len(self)
+        j = i + n if i < 0 else i
+        return ScoreDistribution.from_parts(self.sf(j), self.scale[j], int(self.offset[j]), int(self.rows[j]),
+                                            int(self.min_score[j]), int(self.max_score[j]))
+
+    def thresholds(self, pvalue) -> np.ndarray:
+        """``ScoreDistribution.score`` (dist.rs:104-116) of every motif in one call: float32 ``[n]`` for one p-value, or
+        for one p-value per motif."""
+        n = len(self)
+        p = np.ascontiguousarray(np.broadcast_to(np.asarray(pvalue, dtype=np.float64), (n,)))
+        out = np.zeros(n, dtype=np.float32)
+        check(self._L.lm_hip_dists_scores(self._pli._h, self._h, p.ctypes.data if n else None, out.ctypes.data if n else None))
+        return out
+
+    def pvalues(self, counts, scores=None) -> np.ndarray:
+        """``ScoreDistribution.pvalue`` (dist.rs:91-101) of many scores in one call: float64, one per score.  Either
+        ``(counts, scores)`` -- ``counts[i]`` consecutive float32 scores belong to motif ``i`` -- or the ``SetHits`` /
+        ``BatchHits`` of a scan of the same motifs, whose score column is read where it lies."""
+        if scores is None:
+            hits = counts
+            counts = hits.counts
+            scores = hits.hits["score"] if isinstance(hits, SetHits) else hits.values
+        counts = np.ascontiguousarray(counts, dtype=np.uintp)
+        if counts.shape != (len(self),):
+            raise ValueError("one count per motif")
+        scores = np.asarray(scores)
+        if scores.dtype != np.float32 or scores.ndim != 1 or (scores.size > 1 and scores.strides[0] < 4):
+            scores = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+        total = int(counts.sum())
+        if scores.size != total:
+            raise ValueError(f"{total} scores counted, {scores.size} given")
+        out = np.zeros(total, dtype=np.float64)
+        if total:
+            check(self._L.lm_hip_dists_pvalues(self._pli._h, self._h, counts.ctypes.data, scores.ctypes.data,
+                                               scores.strides[0] if total > 1 else 4, out.ctypes.data))
+        return out
 
 
 # --- scores -----------------------------------------------------------------------------

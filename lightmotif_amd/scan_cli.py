@@ -27,6 +27,10 @@ Behaviour follows lightmotif-cli/src/main.rs:
 ``--best`` writes, instead of the hits above a threshold, ONE line per (sequence, strand, motif) that has a window: the
 best window of the motif in that record, the lowest position among equal scores (``Pipeline.scan_best_set``); thresholds
 play no part.
+``--pvalues device`` (the default) builds the score distributions of all motifs on the device
+(``Pipeline.score_distributions``): the thresholds of ``-P`` come from one call, and the ``pvalue`` column of a set from one
+call per strand on the set's hits.  ``--pvalues host`` is the per-motif, per-hit host code of ``dist.py``; the TSV is the
+same byte for byte.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -191,7 +195,7 @@ def best_set(pli: Pipeline, seqset: StripedSequenceSet, batch: MotifBatch):
     return motif.astype(np.int64), res.position[motif, rec], res.score[motif, rec], bounds
 
 
-def main(argv: Optional[Sequence[str]] = None) -> int:
+def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
     ap.add_argument("-s", "--sequences", required=True, help="FASTA file (optionally gzipped)")
@@ -210,6 +214,24 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--ingest", choices=("device", "host"), default="device",
                     help="where the FASTA container is parsed: on the device from the file's bytes (default), or by the "
                          "line-by-line reader on the host")
+    ap.add_argument("--pvalues", choices=("device", "host"), default="device",
+                    help="where p-values become thresholds and scores become p-values: from score distributions built "
+                         "on the device for all motifs at once (default), or motif by motif and hit by hit on the host")
+    return ap
+
+
+def hit_pvalues(dists, motif: np.ndarray, score: np.ndarray) -> np.ndarray:
+    """The p-value of every hit of a set in one ``ScoreDistributions.pvalues`` call: the hits come ordered by record, the
+    call takes them grouped by motif, so they are sorted by motif on the way in and put back on the way out."""
+    order = np.argsort(motif, kind="stable")
+    counts = np.bincount(motif, minlength=len(dists))
+    out = np.empty(len(motif), dtype=np.float64)
+    out[order] = dists.pvalues(counts, np.ascontiguousarray(score[order], dtype=np.float32))
+    return out
+
+
+def main(argv: Optional[Sequence[str]] = None) -> int:
+    ap = build_parser()
     args = ap.parse_args(argv)
 
     print("Loading matrices")
@@ -219,15 +241,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     print(f"Loaded {len(records)} matrices (M={min(lengths, default=0)}..{max(lengths, default=0)})")
     print("Preparing motifs")
     direct = [r.matrix.normalize(0.1).log_odds() for r in records]
-    thresholds = thresholds_for(direct, args.pvalue, args.rel_threshold, args.abs_threshold)
+    if args.batch_bases < 1:
+        ap.error("--batch-bases must be positive")
+    pli = Pipeline.hip(args.device)
+    dists = pli.score_distributions(direct) if args.pvalues == "device" else None
+    if dists is not None and args.rel_threshold is None and args.abs_threshold is None:
+        thresholds = dists.thresholds(1e-5 if args.pvalue is None else args.pvalue).tolist()   # main.rs:479-489
+    else:
+        thresholds = thresholds_for(direct, args.pvalue, args.rel_threshold, args.abs_threshold)
     strands = [("+", direct)]
     if args.reverse:
         strands.append(("-", [p.reverse_complement() for p in direct]))
     max_m = max(lengths, default=0)
-
-    if args.batch_bases < 1:
-        ap.error("--batch-bases must be positive")
-    pli = Pipeline.hip(args.device)
     batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
     n_hits = 0
     opener = _open_bytes if args.ingest == "device" else _open_text
@@ -240,14 +265,18 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         def write_set(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
             seqset.configure_wrap(max_m)                                   # main.rs:543
             found = [(strand, (best_set if args.best else scan_set)(pli, seqset, batch)) for strand, batch in batches]
+            # either strand looks the DIRECT matrix's distribution up (main.rs:335)
+            pvalues = [None if dists is None else hit_pvalues(dists, motif, score) for _, (motif, _, score, _) in found]
             wrote = 0
             for r, name in enumerate(names):
-                for strand, (motif, pos, score, bounds) in found:
+                for (strand, (motif, pos, score, bounds)), pvs in zip(found, pvalues):
                     a, b = int(bounds[r]), int(bounds[r + 1])
-                    for mi, p, s in zip(motif[a:b].tolist(), pos[a:b].tolist(), score[a:b].tolist()):
-                        dist = direct[mi].score_distribution              # main.rs:335: motif.dist
+                    pv = [None] * (b - a) if pvs is None else pvs[a:b].tolist()
+                    for mi, p, s, q in zip(motif[a:b].tolist(), pos[a:b].tolist(), score[a:b].tolist(), pv):
+                        if q is None:
+                            q = direct[mi].score_distribution.pvalue(s)   # main.rs:335: motif.dist
                         out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{p}\t{strand}\t{_fmt_score(s)}\t"
-                                  f"{_fmt_exp(dist.pvalue(s))}\n")
+                                  f"{_fmt_exp(q)}\n")
                     wrote += b - a
             return wrote
 
