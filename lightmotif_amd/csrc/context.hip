@@ -1,6 +1,6 @@
 // context.hip -- the library's plumbing behind include/lightmotif_hip.h: error text, device scratch, the page-locked pool of
 // result blocks, library / device queries and the context (stream, options).  The other parts of the C ABI:
-//   pssm.hip       lm_hip_pssm_*: device tables of a scoring matrix (transposed f32 table, prefilter images)
+//   pssm.hip       lm_hip_pssm_*: the device image of a scoring matrix, built by pssm_tables.hpp (f32 tables, prefilter images)
 //   score_api.hip  Score / Maximum / Threshold on device pointers, the fused and batched scans
 //   handles.hip    resident StripedSequence / StripedScores handles, host -> device ingest
 //   hostptr.hip    the host-pointer entry points a reference-side shim binds

@@ -326,6 +326,9 @@ struct lm_hip_pssm {
     int device = 0;
     size_t m = 0, k = 0;
     std::vector<float> host;  // m x k, dense (row-major, stride k)
+    // The one device allocation of the matrix: the image of pssm_tables.hpp.  Every d_* pointer below is a view into it
+    // (nullptr: the matrix has no such table); lm_hip_pssm_destroy frees the slab alone.
+    unsigned char *d_slab = nullptr;
     // Transposed, padded copy for the C=32 kernels: table[s * ts + j] = pssm[j][s],
     // ts = floats per symbol row (multiple of 4, ts/4 odd), zero padded.
     float *d_table = nullptr;

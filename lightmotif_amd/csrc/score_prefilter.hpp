@@ -22,7 +22,7 @@
 // P = -inf, off_j = min_s P'[j][s], O = sum off_j, factor = (sum_j max_s P'[j][s] - O)
 // / kPrefilterTop, d[j][s] = ceil((P'[j][s] - off_j) / factor), an f32 score S >= t implies
 // sum d >= floor((t - O) / factor) - ceil(E / factor) where E bounds the rounding error
-// of the M sequential f32 adds (host side, pssm.hip: build_prefilter).
+// of the M sequential f32 adds (host side, pssm_tables.hpp: build_prefilter).
 //
 // Rotating accumulators as in score_c32, with the motif padded to an EVEN length MP by
 // a leading all-zero row (SHIFT = MP - M): slot pair i = outputs (2i, 2i+1) mod MP.

@@ -40,7 +40,7 @@ def min_length(regime):
 
 
 def no_overflow_limit(m):
-    """The prefilter's limit on the sum of the rows' largest finite |w| (pssm.hip, build_prefilter): below it no
+    """The prefilter's limit on the sum of the rows' largest finite |w| (csrc/pssm_tables.hpp, build_prefilter): below it no
     partial sum of a window can round to +-inf."""
     return FLT_MAX / (1.0 + (m + 1) * 2.0 ** -23)
 
@@ -53,7 +53,8 @@ def abs_sum(pssm, k):
 
 
 def prefilter_sound(pssm, k):
-    """Whether build_prefilter makes a discrete image of this matrix (mirror of its conditions)."""
+    """Whether build_pssm_tables (csrc/pssm_tables.hpp) gives this matrix prefilter images: an independent restatement of
+    build_prefilter's conditions, which tests/cpp/test_pssm_tables.cpp checks on the builder itself."""
     w = np.asarray(pssm[:, :k], np.float64)
     if w.shape[0] < 1 or np.isnan(w).any() or np.isposinf(w).any():
         return False
@@ -182,7 +183,7 @@ def extra_thresholds(regime):
 
 def prefilter_td(pssm, k, t):
     """The discrete threshold the fused threshold route derives from ``t`` (score_threshold.hip, mirror of its map
-    with build_prefilter's offset / factor / error bound); a value below 1 means the route cannot be taken."""
+    with the offset / factor / error bound of build_prefilter, csrc/pssm_tables.hpp); a value below 1 means the route cannot be taken."""
     w = np.asarray(pssm[:, :k], np.float64)
     fin = np.where(np.isneginf(w), np.nan, w)
     lo, hi = np.nanmin(fin, axis=1), np.nanmax(fin, axis=1)
@@ -193,7 +194,7 @@ def prefilter_td(pssm, k, t):
 
 
 def discrete_weights(pssm, k):
-    """The u16 weights of build_prefilter's image (ceil((w - row min) / factor), at least the guard's +1 on exact
+    """The u16 weights of the images build_pssm_tables packs (csrc/pssm_tables.hpp, build_prefilter: ceil((w - row min) / factor), at least the guard's +1 on exact
     multiples; -inf -> 0), computed whether or not the matrix passes the no-overflow limit."""
     w = np.asarray(pssm[:, :k], np.float64)
     fin = np.where(np.isneginf(w), np.nan, w)

@@ -7,7 +7,7 @@ subnormal weights, signed zeros and weights within an ulp of 1000.  Thresholds: 
 smallest subnormal, realised scores and their f32 neighbours, the window bound B (best_kmer_score) and just above it.
 
 The fused routes scan a 16-bit image of the matrix and re-score what it flags; that image is sound only while no
-partial sum can overflow (pssm.hip, build_prefilter).  Each parametrisation forces its route through a pipeline with
+partial sum can overflow (pssm_tables.hpp, build_prefilter).  Each parametrisation forces its route through a pipeline with
 its own options and checks ``last_kernel`` after a threshold the route can serve: the prefilter kernel where a sound
 image exists and the threshold maps into its range (mirrored by extreme_weights.prefilter_td), never otherwise."""
 import os

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Host share of the fused calls, library A against library B on one box: the fused threshold call at 1 Mbp / 100 Mbp /
 1 Gbp (M = 20, p = 1e-5), the fused argmax at 1 Gbp, the configs[0] small argmax (C ABI, C = 32 and C = 1) and the
-2 346-motif x 100 Mbp threshold and argmax batches.  Every round starts a fresh child process per library in the order
+2 346-motif x 100 Mbp threshold and argmax batches, and creating + destroying the device handles of those 2 346 matrices
+(pssm_create_jaspar).  Every round starts a fresh child process per library in the order
 A, B, A (LM_HIP_LIBRARY selects the library; the second A is the A/A control); a child warms every call up once and
 reports the median wall time of each.  The table holds, per call, the medians over the rounds of A and B, their
 difference, and the A/A differences (of the medians, and the largest of a round).
@@ -29,13 +30,13 @@ def child():
     from lightmotif_amd import _ffi, io as lmio
     from bench_configs import motif, resident_sequence
 
-    def med(fn, reps, warm=1):
-        for _ in range(warm):
-            fn()
+    def med(fn, reps, warm=1, setup=None):
+        """Median wall time of `fn` in us; `setup` runs before every repetition, untimed, and hands `fn` its argument."""
         ts = []
-        for _ in range(reps):
-            t0 = time.perf_counter(); fn(); ts.append(time.perf_counter() - t0)
-        return round(float(np.median(ts)) * 1e6, 2)
+        for rep in range(warm + reps):
+            args = (setup(),) if setup else ()
+            t0 = time.perf_counter(); fn(*args); ts.append(time.perf_counter() - t0)
+        return round(float(np.median(ts[warm:])) * 1e6, 2)
 
     torch.cuda.set_device(0)
     pli = lm.Pipeline.hip(0, stream=torch.cuda.current_stream().cuda_stream)
@@ -68,6 +69,16 @@ def child():
     batch = pli.prepare_batch(pssms, [p.score_for_pvalue(1e-5) for p in pssms])
     out["c3_threshold_batch"] = med(lambda: pli.scan_threshold_batch(batch, None, seq), 12, 2)
     out["c3_argmax_batch"] = med(lambda: pli.scan_argmax_batch(pssms, seq), 12, 2)
+    # the device handles of those matrices, created and destroyed on a fresh pipeline
+    def create_destroy(p):
+        handles = []
+        for q in pssms:
+            h = C.c_void_p()
+            _ffi.check(p._L.lm_hip_pssm_create(p._h, q.data.ctypes.data, q.data.shape[0], q.data.shape[1], q.k, C.byref(h)))
+            handles.append(h)
+        for h in handles:
+            p._L.lm_hip_pssm_destroy(h)
+    out["pssm_create_jaspar"] = med(create_destroy, 5, 1, setup=lambda: lm.Pipeline.hip(0))
     print("RESULT " + json.dumps(out), flush=True)
 
 
