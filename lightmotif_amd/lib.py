@@ -313,12 +313,14 @@ class Pipeline:
         out.header_spans = self._take_array(spans, 2 * n.value, np.uint64).reshape(n.value, 2)
         return out
 
-    def stripe_set(self, encoded: Sequence["EncodedSequence"], columns: int = DEFAULT_COLUMNS) -> "StripedSequenceSet":
-        """The same from already encoded records (``lm_hip_seqset_from_encoded``)."""
-        protein = {e.protein for e in encoded}
-        if len(protein) > 1:
+    def stripe_set(self, encoded: Sequence["EncodedSequence"], columns: int = DEFAULT_COLUMNS,
+                   protein: Optional[bool] = None) -> "StripedSequenceSet":
+        """The same from already encoded records (``lm_hip_seqset_from_encoded``).  ``protein`` names the alphabet of a set
+        without records (DNA when left out); with records it must be theirs."""
+        alphabets = {e.protein for e in encoded} | ({bool(protein)} if protein is not None else set())
+        if len(alphabets) > 1:
             raise ValueError("the records of a set share one alphabet")
-        protein = bool(protein.pop()) if protein else False
+        protein = bool(alphabets.pop()) if alphabets else False
         parts = [np.ascontiguousarray(e.data, dtype=np.uint8) for e in encoded]
         offs = np.zeros(len(parts) + 1, dtype=np.uint64)
         np.cumsum([p.size for p in parts], out=offs[1:])

@@ -424,6 +424,26 @@ def test_misuse_is_a_status(pli):
     assert "sequence 2 at position 6" in str(bad.value)
 
 
+def test_a_set_without_records_keeps_its_alphabet(pli):
+    """An empty list of encoded records says nothing about its alphabet: ``stripe_set(..., protein=True)`` names it, and
+    the empty protein set then takes protein motifs like the empty sets of the other two builders (seeds 17 and 32 of
+    tests/test_gpu_seqset_fuzz.py are such sets; without the argument the encoded builder made a DNA set of them)."""
+    rng = np.random.default_rng(13)
+    prot = lm.ScoringMatrix(make_matrix(rng, 8, 21), protein=True)
+    sets = [pli.stripe_set([], protein=True), pli.stripe_ascii_set([], protein=True), pli.stripe_fasta_set(b"", protein=True)]
+    for s in sets:
+        s.configure_wrap(7)
+        assert s.protein and len(s) == 0 and s.total_length == 0 and s.rows == 0 and s._info()[5] == 21
+        res = pli.scan_threshold_set([prot], [-np.inf], s)
+        assert res.total == 0 and res.counts.tolist() == [0]
+        assert pli.scan_best_set([prot], s).found.shape == (1, 0)
+    assert not pli.stripe_set([]).protein                                  # DNA when nothing is said
+    with pytest.raises(ValueError):                                        # records of the other alphabet
+        pli.stripe_set([lm.EncodedSequence(np.zeros(4, np.uint8))], protein=True)
+    one = pli.stripe_set([lm.EncodedSequence(np.zeros(9, np.uint8), protein=True)], protein=True)
+    assert one.protein and one.lengths.tolist() == [9]
+
+
 def test_the_set_beats_the_per_record_loop(pli):
     """2 000 records x 500 bp x 64 JASPAR motifs at p = 1e-5: one resident set + one call (B) against the loop of 2 000
     synchronising calls it replaces (A), medians of 5 alternating runs after a warm-up.  The margin is 1 x: anything not
