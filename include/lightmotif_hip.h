@@ -170,7 +170,9 @@ int lm_hip_ctx_set_track_argmax(lm_hip_ctx *ctx, int enabled);
  * "short_order", "time_scan", "drop_last", "list_scan_max" (0 = Scanner::max always walks windows of materialised u8 scores),
  * "block_prefilter" (0 = the protein one-symbol scans load a byte per lane and row
  * instead of 4-row blocks), "poll_done" (1 = a single fused threshold call polls the word the ranking kernel raises in pinned
- * memory instead of waiting for its stream: 3-4 us less per call, unless the caller synchronises the device right behind it); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
+ * memory instead of waiting for its stream: 3-4 us less per call, unless the caller synchronises the device right behind it),
+ * "count_tile_rows" (rows per block of the table behind lm_hip_seq_count_symbols / lm_hip_seqset_count_symbols, 1 ... 65536;
+ * 0 = the default of 1024: a small value makes a small input span many blocks of the table and of its scan); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
  * LM_HIP_ERR_BAD_ARGS.  The shipped library reads none of them from the environment. */
 int lm_hip_ctx_set_option(lm_hip_ctx *ctx, const char *name, double value);
 /* Round-4 ABI: selected an XCD-aware workgroup remap of the store kernel, which measured slower and was removed in round 5.
@@ -195,7 +197,8 @@ int lm_hip_ctx_last_scan_kernel_ms(lm_hip_ctx *ctx, float *ms);
 /* Diagnostic ("time_scan" = 1): the last fused THRESHOLD call (single or batched) by phase, in ms -- [0] the scan kernels,
  * [1] the exact re-scoring of their candidates, [2] the kernels that order the hit list (HIP events on the context's
  * stream), [3] the rest of the call on the host clock: enqueueing, the synchronisation's wake-up, the copy of the results
- * out of the pinned block.  -1 where nothing was recorded. */
+ * out of the pinned block.  -1 where nothing was recorded.  After lm_hip_seq_count_symbols / lm_hip_seqset_count_symbols:
+ * [0] the block pass, [1] the scan of its table, [2] the prefix pass and the differences, [3] -1. */
 int lm_hip_ctx_last_phases_ms(lm_hip_ctx *ctx, float phases[4]);
 /* Diagnostic: what the scan kernel of the last SINGLE-job fused call on this context looked up per position -- the motif
  * rows it scanned (a pair scan of M = 20, 24, ... 36 may look M - 1 rows up and credit the last one with its best weight)
@@ -460,6 +463,31 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
  * throughout. */
 int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set,
                             lm_hip_set_best *best);
+
+/* SymbolCount::count_symbols of a StripedSequence (seq.rs:444-483, the loop of seq.rs:466-482), and the same for every
+ * record of a set in ONE call: what Background::from_sequence / from_sequences (abc.rs:404-456) count before
+ * Background::from_counts (abc.rs:389-402) turns the table into frequencies, on the resident bytes (csrc/composition.hip).
+ *   positions   position p of the sequence (of the concatenation, for a set) sits at row p % rows, column p / rows, with
+ *               rows = matrix().rows() - wrap() = ceil(length / cols) (pli/mod.rs:178-200).  Exactly the positions
+ *               p < length are counted: the cells of the padded tail are not, although they hold the default symbol, and
+ *               neither are the wrap rows (seq.rs:469-477) -- the result is the same before and after configure_wrap
+ *   sets        record r owns positions [offsets[r], offsets[r + 1]); an empty record gives a row of zeros, the sum of
+ *               row r is the record's length and the sum of the table is total_length
+ *   counts      the caller's memory, row-major: k entries for a sequence, counts[r * k + s] (records * k entries) for a
+ *               set, k = the handle's alphabet size; `capacity` is in ELEMENTS, LM_HIP_ERR_CAPACITY with nothing written
+ *               when it is short
+ *   bytes >= k  (possible in an adopted matrix, or one written through its device pointer) are counted in no bin and
+ *               index nothing; the sum of a row is then smaller than the length
+ *   empty       zero records: LM_HIP_OK, nothing written; length == 0: LM_HIP_OK, zeros written; no launch either way
+ * LM_HIP_ERR_BAD_ARGS, with a message and before any device work, for a null ctx, handle or counts, for a handle that
+ * lives on another device than the context, and for an adopted matrix described as holding more symbols than its cells.
+ * Every position and count is 64-bit; the result is identical from call to call.  Each call enqueues on the context's
+ * stream and synchronises it; lm_hip_ctx_last_kernel names the counting kernel ("count_blocks") afterwards.
+ * TEMPORARY DEVICE MEMORY, from the context's scratch (handed back above 2 GB like every other call's): a table of
+ * 12 k / T bytes per position (T = 1024 rows per block, the option "count_tile_rows": 0.06 bytes per position for DNA,
+ * 0.25 for protein) and 16 k bytes per record.  The pass reads 1 byte per position. */
+int lm_hip_seq_count_symbols(lm_hip_ctx *ctx, const lm_hip_seq *seq, uint64_t *counts, size_t capacity);
+int lm_hip_seqset_count_symbols(lm_hip_ctx *ctx, const lm_hip_seqset *set, uint64_t *counts, size_t capacity);
 
 /* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
  * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the

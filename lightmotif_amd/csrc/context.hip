@@ -354,7 +354,7 @@ int lm_hip_device_clock_mhz(int device, unsigned window_us, double *mhz)
 static const char *const kOptionNames[] = {"track_argmax", "xlong_store", "host_fold", "speculate_order", "suffix_argmax",
                                            "multi_motif", "quad_loads", "skip_unreachable", "pair_prefilter",
                                            "pair_prefilter_protein", "chunked_fused", "chunk_rows", "tiled",
-                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done"};
+                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done", "count_tile_rows"};
 
 static int set_option(lm_hip_ctx *ctx, const char *name, double value)
 {
@@ -385,6 +385,10 @@ static int set_option(lm_hip_ctx *ctx, const char *name, double value)
         if (!(value >= 64) || !(value <= 2147483648.0))  // (also rejects NaN and +inf: the cast below must be defined)
             return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: chunk_rows must be 64 ... 2^31");
         ctx->chunk_rows = (size_t)value;
+    } else if (n == "count_tile_rows") {  // rows per block of count_symbols' table (composition.hip); 0 = the default
+        if (!(value >= 0) || !(value <= 65536.0))
+            return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: count_tile_rows must be 0 ... 65536");
+        ctx->count_tile_rows = (size_t)value;
     } else if (n == "suffix_occurrences") {
         ctx->suffix_occurrences = value > 0 ? value : 0;
     } else {

@@ -180,6 +180,14 @@ public:
         check(lm_hip_seq_download(ctx_->ctx, h_, m.ptr()));
         return m;
     }
+    // SymbolCount::count_symbols (seq.rs:444-483) on the device: A::K counts in alphabet order over the positions
+    // p < len() -- neither the padded tail nor the wrap rows
+    std::vector<uint64_t> count_symbols() const
+    {
+        std::vector<uint64_t> out(A::K);
+        check(lm_hip_seq_count_symbols(ctx_->ctx, h_, out.data(), out.size()));
+        return out;
+    }
     lm_hip_seq *handle() const { return h_; }
 
 private:
@@ -235,6 +243,14 @@ public:
     }
     // seq.rs:369-381 on the set's matrix
     void configure_wrap(size_t m) { check(lm_hip_seqset_configure_wrap(ctx_->ctx, h_, m)); }
+    // SymbolCount::count_symbols (seq.rs:444-483) of every record in one call: records() x A::K, row-major
+    std::vector<uint64_t> count_symbols() const
+    {
+        std::vector<uint64_t> out(records() * A::K);
+        uint64_t none = 0;
+        check(lm_hip_seqset_count_symbols(ctx_->ctx, h_, out.empty() ? &none : out.data(), out.size()));
+        return out;
+    }
     lm_hip_seqset *handle() const { return h_; }
 
 private:
@@ -257,6 +273,30 @@ inline std::vector<float> uniform_background()  // abc.rs:473-487
 {
     std::vector<float> bg(A::K, 1.0f / (float)(A::K - 1));
     bg[A::K - 1] = 0.0f;
+    return bg;
+}
+
+// Background::from_counts (abc.rs:389-402) behind the filter of from_sequence / from_sequences (abc.rs:422-456): `counts`
+// holds one row of A::K symbol counts or several (a set's table), which are summed; the default symbol's count is dropped
+// unless `unknown`; each frequency is `count as f32 / total as f32`.  Throws InvalidData when nothing is left to count.
+template <class A>
+inline std::vector<float> background_from_counts(const std::vector<uint64_t> &counts, bool unknown = false)
+{
+    if (counts.size() % A::K != 0)
+        throw InvalidData();
+    uint64_t sums[A::K] = {};
+    for (size_t i = 0; i < counts.size(); ++i)
+        sums[i % A::K] += counts[i];
+    if (!unknown)
+        sums[A::K - 1] = 0;
+    uint64_t total = 0;
+    for (uint64_t c : sums)
+        total += c;
+    if (total == 0)
+        throw InvalidData();
+    std::vector<float> bg(A::K);
+    for (size_t s = 0; s < A::K; ++s)
+        bg[s] = (float)sums[s] / (float)total;
     return bg;
 }
 

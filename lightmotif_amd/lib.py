@@ -27,6 +27,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 __all__ = [
     "pack_2bit", "fasta_names",
     "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "background_from_counts",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -658,6 +659,44 @@ def default_pipeline() -> Pipeline:
 # --- sequences ----------------------------------------------------------------------
 
 
+def background_from_counts(counts, unknown: bool = False) -> np.ndarray:
+    """``Background::from_counts`` (abc.rs:389-402) behind the filter of ``from_sequence`` / ``from_sequences``
+    (abc.rs:422-456): ``counts`` is one row of ``k`` symbol counts or a ``(records, k)`` table, whose rows are summed; the
+    default symbol's count is dropped unless ``unknown``; each frequency is ``count as f32 / total as f32`` with the integer
+    total -- one conversion each, one f32 divide.  ``ValueError`` when nothing is left to count (``InvalidData``)."""
+    table = np.asarray(counts)
+    if table.dtype.kind not in "iu":
+        raise TypeError("symbol counts are integers")
+    table = table.astype(np.uint64 if table.dtype.kind == "u" else np.int64)
+    if table.ndim == 2:
+        table = table.sum(axis=0, dtype=table.dtype)
+    if table.ndim != 1 or table.size < 2:
+        raise ValueError("symbol counts: k entries, or a (records, k) table")
+    if (table < 0).any():
+        raise ValueError("symbol counts cannot be negative")
+    if not unknown:
+        table[-1] = 0           # abc.rs:429: `unknown || c != n`
+    total = table.sum(dtype=table.dtype)
+    if total == 0:
+        raise ValueError("cannot build a background from a table without counts")
+    return table.astype(np.float32) / total.astype(np.float32)
+
+
+def _count_symbols(call, ctx, handle, records: int, k: int) -> np.ndarray:
+    out = np.zeros(records * k, dtype=np.int64)     # (the library writes u64: a count never reaches 2^63)
+    # (an empty table still needs a pointer: NULL is a misuse of the entry point, zero records are not)
+    buf = out if out.size else np.zeros(1, dtype=np.int64)
+    check(call(ctx, handle, buf.ctypes.data, out.size))
+    return out.reshape(records, k)
+
+
+def _symbol_index(symbol: str, protein: bool) -> int:
+    i = _symbols(protein).find(symbol) if isinstance(symbol, str) and len(symbol) == 1 else -1
+    if i < 0:
+        raise ValueError(f"Invalid symbol: {symbol!r}")
+    return i
+
+
 class EncodedSequence:
     """seq.rs:83-98: a vector of symbol indices (host side; 1 byte per symbol)."""
 
@@ -708,6 +747,10 @@ class EncodedSequence:
 
     def copy(self) -> "EncodedSequence":
         return EncodedSequence(self.data.copy(), protein=self.protein)
+
+    def count_symbols(self) -> np.ndarray:
+        """seq.rs:61-70 ``SymbolCount`` of the host array: ``k`` counts (int64) in alphabet order."""
+        return np.bincount(self.data, minlength=_k(self.protein))[:_k(self.protein)].astype(np.int64)
 
     __copy__ = copy
 
@@ -782,6 +825,20 @@ class StripedSequence:
 
     __copy__ = copy
 
+    def count_symbols(self) -> np.ndarray:
+        """seq.rs:444-483 ``SymbolCount::count_symbols`` on the device (``lm_hip_seq_count_symbols``): ``k`` counts (int64)
+        in alphabet order over the positions ``p < len(self)`` -- neither the padded tail nor the wrap rows."""
+        L = self._pli._L
+        return _count_symbols(L.lm_hip_seq_count_symbols, self._pli._h, self._h, 1, _k(self.protein))[0]
+
+    def count_symbol(self, symbol: str) -> int:
+        """seq.rs:445-449 ``SymbolCount::count_symbol``."""
+        return int(self.count_symbols()[_symbol_index(symbol, self.protein)])
+
+    def background(self, unknown: bool = False) -> np.ndarray:
+        """``Background::from_sequence`` (abc.rs:422-434) of the resident sequence: ``k`` f32 frequencies."""
+        return background_from_counts(self.count_symbols(), unknown)
+
     def __array__(self, dtype=None, copy=None):
         """What the reference exposes through ``memoryview(striped)``: shape ``(columns, rows)`` with
         strides ``(1, stride)`` (lib.rs:303-317), i.e. indexed ``[column, row]``; a host copy here, the
@@ -841,6 +898,15 @@ class StripedSequenceSet:
         """seq.rs:369-381 on the set's matrix"""
         check(self._pli._L.lm_hip_seqset_configure_wrap(self._pli._h, self._h, m))
 
+    def count_symbols(self) -> np.ndarray:
+        """``SymbolCount::count_symbols`` (seq.rs:444-483) of every record in one call (``lm_hip_seqset_count_symbols``):
+        a ``(records, k)`` int64 table; row ``r`` sums to the record's length."""
+        return _count_symbols(self._pli._L.lm_hip_seqset_count_symbols, self._pli._h, self._h, len(self), _k(self.protein))
+
+    def background(self, unknown: bool = False) -> np.ndarray:
+        """``Background::from_sequences`` (abc.rs:441-456) of the set's records: ``k`` f32 frequencies."""
+        return background_from_counts(self.count_symbols(), unknown)
+
 
 # --- matrices ------------------------------------------------------------------------
 
@@ -892,8 +958,8 @@ class CountMatrix:
     def __eq__(self, other) -> bool:
         return isinstance(other, CountMatrix) and np.array_equal(self.data, other.data)
 
-    def normalize(self, pseudocount: Union[None, float, Dict[str, float]] = None) -> "WeightMatrix":
-        """lib.rs:501-526: ``to_freq(pseudo).to_weight(None)`` in f32."""
+    def _to_freq(self, pseudocount: Union[None, float, Dict[str, float]]) -> np.ndarray:
+        """pwm/mod.rs:240-258 ``to_freq(pseudo)`` in f32."""
         k = self.data.shape[1]
         f32 = np.float32
         if pseudocount is None:
@@ -903,7 +969,6 @@ class CountMatrix:
         else:  # abc.rs:558-573: every symbol but the default one
             pseudo = np.full(k, f32(pseudocount), dtype=f32)
             pseudo[k - 1] = 0
-        bg = uniform_background(k)
         out = np.zeros((len(self), k), dtype=f32)
         for i in range(len(self)):
             row = (self.data[i].astype(f32) + pseudo).astype(f32)  # pwm/mod.rs:249-251
@@ -911,9 +976,40 @@ class CountMatrix:
             for x in row:                                            # :252 sequential f32 sum
                 total = f32(total + x)
             with np.errstate(divide="ignore", invalid="ignore"):
-                row = (row / total).astype(f32)                      # :253-255
-                out[i] = np.where(bg == 0, f32(0), row / np.where(bg == 0, f32(1), bg))  # :384-390
+                out[i] = (row / total).astype(f32)                   # :253-255
+        return out
+
+    def normalize(self, pseudocount: Union[None, float, Dict[str, float]] = None) -> "WeightMatrix":
+        """lib.rs:501-526: ``to_freq(pseudo).to_weight(None)`` in f32."""
+        f32 = np.float32
+        freq = self._to_freq(pseudocount)
+        bg = uniform_background(freq.shape[1])
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = np.where(bg == 0, f32(0), freq / np.where(bg == 0, f32(1), bg)).astype(f32)  # :384-390
         return WeightMatrix(out, bg, protein=self.protein)
+
+    def to_scoring(self, pseudocount: Union[None, float, Dict[str, float]] = None,
+                   background: Union[None, Dict[str, float], np.ndarray] = None) -> "ScoringMatrix":
+        """``to_freq(pseudo)`` (pwm/mod.rs:240-258) then ``into_scoring(background)`` (pwm/mod.rs:415-430): per cell
+        ``log2(freq / f)`` in f32, and ``-inf`` where the background frequency ``f`` is zero.  ``background`` is a dict of
+        frequencies or an array of ``k`` of them (e.g. ``background_from_counts``); ``None`` is the uniform background, and
+        the result is then ``normalize(pseudocount).log_odds()`` bit for bit.  This is NOT ``log_odds(background=...)``, the
+        reference's ``rescale`` (pwm/mod.rs:471-492), which makes the default symbol's column ``0 * (0 / 0) = NaN``."""
+        f32 = np.float32
+        freq = self._to_freq(pseudocount)
+        k = freq.shape[1]
+        if background is None:
+            bg = uniform_background(k)
+        elif isinstance(background, dict):
+            bg = _dict_to_rows({a: [b] for a, b in background.items()}, self.protein, f32)[0]
+        else:
+            bg = np.array(background, dtype=f32)
+            if bg.shape != (k,):
+                raise ValueError(f"a background of {k} frequencies is needed")
+        with np.errstate(divide="ignore", invalid="ignore"):
+            odds = (freq / np.where(bg == 0, f32(1), bg)).astype(f32)
+            out = np.where(bg == 0, f32(-np.inf), np.log2(odds, dtype=f32)).astype(f32)
+        return ScoringMatrix(out, bg, protein=self.protein)
 
 
 def uniform_background(k: int) -> np.ndarray:

@@ -31,12 +31,20 @@ play no part.
 (``Pipeline.score_distributions``): the thresholds of ``-P`` come from one call, and the ``pvalue`` column of a set from one
 call per strand on the set's hits.  ``--pvalues host`` is the per-motif, per-hit host code of ``dist.py``; the TSV is the
 same byte for byte.
+``--background sequences`` scores against the composition of the input instead of the uniform background: a first pass
+over the FASTA file (with the chosen ``--ingest``) makes every chunk a resident set, adds its
+``StripedSequenceSet.count_symbols()`` -- counted on the device -- into one total and drops the set; the background is
+``background_from_counts(total)`` (abc.rs:441-456, the unknown symbol left out), the matrices are
+``to_freq(0.1).to_scoring(background)`` (pwm/mod.rs:415-430), and thresholds and the ``pvalue`` column come from the
+distributions of THOSE matrices.  The second pass scans as before.  ``--composition PATH`` writes, during the scan pass,
+one TSV line per record: ``seq_index seq_name length`` and one count per symbol in alphabet order (``A C T G N``).
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
 from __future__ import annotations
 
 import argparse
+import contextlib
 import gzip
 import sys
 from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
@@ -44,7 +52,8 @@ from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
 import numpy as np
 
 from . import io as lmio
-from .lib import MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet, fasta_names
+from .lib import (DNA_SYMBOLS, MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet, background_from_counts,
+                  fasta_names)
 
 DEFAULT_BATCH_BASES = 100_000_000
 
@@ -217,6 +226,11 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--pvalues", choices=("device", "host"), default="device",
                     help="where p-values become thresholds and scores become p-values: from score distributions built "
                          "on the device for all motifs at once (default), or motif by motif and hit by hit on the host")
+    ap.add_argument("--background", choices=("uniform", "sequences"), default="uniform",
+                    help="background frequencies of the scoring matrices and their score distributions: uniform (default), "
+                         "or the composition of the input, counted on the device in a first pass over the file")
+    ap.add_argument("--composition", metavar="PATH",
+                    help="also write a TSV with one line per record: seq_index, seq_name, length and the count of every symbol")
     return ap
 
 
@@ -240,10 +254,45 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     lengths = [len(r.matrix) for r in records]
     print(f"Loaded {len(records)} matrices (M={min(lengths, default=0)}..{max(lengths, default=0)})")
     print("Preparing motifs")
-    direct = [r.matrix.normalize(0.1).log_odds() for r in records]
     if args.batch_bases < 1:
         ap.error("--batch-bases must be positive")
     pli = Pipeline.hip(args.device)
+
+    def sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
+        """One pass over the FASTA file: (index of the first record, names, resident set) per chunk."""
+        with (_open_bytes if args.ingest == "device" else _open_text)(args.sequences) as fasta:
+            if args.ingest == "device":
+                first = 0
+                for chunk in fasta_chunks(fasta, args.batch_bases):
+                    seqset = pli.stripe_fasta_set(chunk, lossy=True)
+                    names = fasta_names(chunk, seqset.header_spans)
+                    if names:
+                        yield first, names, seqset
+                    first += len(names)
+            else:
+                # the rule of batch_records, applied as the records stream in
+                first, names, texts, bases = 0, [], [], 0
+                for name, text in read_fasta(fasta):
+                    if bases > 0 and bases + len(text) > args.batch_bases:
+                        yield first, names, pli.stripe_ascii_set(texts, lossy=True)
+                        first, names, texts, bases = first + len(names), [], [], 0
+                    names.append(name)
+                    texts.append(text)
+                    bases += len(text)
+                if names:
+                    yield first, names, pli.stripe_ascii_set(texts, lossy=True)
+
+    if args.background == "sequences":
+        total = np.zeros(len(DNA_SYMBOLS), dtype=np.int64)
+        for _, _, seqset in sets():
+            total += seqset.count_symbols().sum(axis=0)
+        try:
+            background = background_from_counts(total, unknown=False)          # abc.rs:441-456
+        except ValueError:
+            ap.error(f"--background sequences: {args.sequences} holds no base to count")
+        direct = [r.matrix.to_scoring(0.1, background) for r in records]       # pwm/mod.rs:240-258, 415-430
+    else:
+        direct = [r.matrix.normalize(0.1).log_odds() for r in records]
     dists = pli.score_distributions(direct) if args.pvalues == "device" else None
     if dists is not None and args.rel_threshold is None and args.abs_threshold is None:
         thresholds = dists.thresholds(1e-5 if args.pvalue is None else args.pvalue).tolist()   # main.rs:479-489
@@ -255,18 +304,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     max_m = max(lengths, default=0)
     batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
     n_hits = 0
-    opener = _open_bytes if args.ingest == "device" else _open_text
-    with open(args.output, "w") as out, opener(args.sequences) as fasta:
+    with contextlib.ExitStack() as files:
+        out = files.enter_context(open(args.output, "w"))
         out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue\n")
-
-        def flush(first_index: int, names: List[str], texts: List[str]) -> int:
-            return write_set(first_index, names, pli.stripe_ascii_set(texts, lossy=True))
+        composition = files.enter_context(open(args.composition, "w")) if args.composition else None
+        if composition is not None:
+            composition.write("seq_index\tseq_name\tlength\t" + "\t".join(DNA_SYMBOLS) + "\n")
 
         def write_set(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
             seqset.configure_wrap(max_m)                                   # main.rs:543
             found = [(strand, (best_set if args.best else scan_set)(pli, seqset, batch)) for strand, batch in batches]
             # either strand looks the DIRECT matrix's distribution up (main.rs:335)
             pvalues = [None if dists is None else hit_pvalues(dists, motif, score) for _, (motif, _, score, _) in found]
+            if composition is not None:
+                table = seqset.count_symbols().tolist()
+                for r, (name, length) in enumerate(zip(names, seqset.lengths.tolist())):
+                    composition.write(f"{first_index + r + 1}\t{name}\t{length}\t" + "\t".join(map(str, table[r])) + "\n")
             wrote = 0
             for r, name in enumerate(names):
                 for (strand, (motif, pos, score, bounds)), pvs in zip(found, pvalues):
@@ -280,26 +333,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     wrote += b - a
             return wrote
 
-        if args.ingest == "device":
-            first = 0
-            for chunk in fasta_chunks(fasta, args.batch_bases):
-                seqset = pli.stripe_fasta_set(chunk, lossy=True)
-                names = fasta_names(chunk, seqset.header_spans)
-                if names:
-                    n_hits += write_set(first, names, seqset)
-                first += len(names)
-        else:
-            # the rule of batch_records, applied as the records stream in
-            first, names, texts, bases = 0, [], [], 0
-            for name, text in read_fasta(fasta):
-                if bases > 0 and bases + len(text) > args.batch_bases:
-                    n_hits += flush(first, names, texts)
-                    first, names, texts, bases = first + len(names), [], [], 0
-                names.append(name)
-                texts.append(text)
-                bases += len(text)
-            if names:
-                n_hits += flush(first, names, texts)
+        for first, names, seqset in sets():
+            n_hits += write_set(first, names, seqset)
     print(f"Wrote {n_hits} hits to {args.output}")
     return 0
 
