@@ -172,7 +172,10 @@ int lm_hip_ctx_set_track_argmax(lm_hip_ctx *ctx, int enabled);
  * instead of 4-row blocks), "poll_done" (1 = a single fused threshold call polls the word the ranking kernel raises in pinned
  * memory instead of waiting for its stream: 3-4 us less per call, unless the caller synchronises the device right behind it),
  * "count_tile_rows" (rows per block of the table behind lm_hip_seq_count_symbols / lm_hip_seqset_count_symbols, 1 ... 65536;
- * 0 = the default of 1024: a small value makes a small input span many blocks of the table and of its scan); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
+ * 0 = the default of 1024: a small value makes a small input span many blocks of the table and of its scan),
+ * "tally_launches" (1 = count the registry rows launched, lm_hip_ctx_launch_tally), "track_fold_cells" (score_into on handles
+ * stores + tracks the maximum in ONE launch below this many cells and with block maxima + two reduction launches from it on;
+ * default 8 Mi, 0 = always the latter: lets a small input take the large inputs' route); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
  * LM_HIP_ERR_BAD_ARGS.  The shipped library reads none of them from the environment. */
 int lm_hip_ctx_set_option(lm_hip_ctx *ctx, const char *name, double value);
 /* Round-4 ABI: selected an XCD-aware workgroup remap of the store kernel, which measured slower and was removed in round 5.
@@ -205,6 +208,31 @@ int lm_hip_ctx_last_phases_ms(lm_hip_ctx *ctx, float phases[4]);
  * and the bytes of LDS table that costs (what a roofline figure must be priced against).  Zeros: no such scan ran (a batch,
  * an argmax settled from the last rows, a chunked route).  Either pointer may be NULL. */
 int lm_hip_ctx_last_scan_info(lm_hip_ctx *ctx, size_t *motif_rows_scanned, size_t *lds_bytes_per_position);
+/* One row of the library's registry of unrolled kernels: a kernel family, the alphabet width it is built for (1 = more than
+ * 16 symbols), the motif length M it is instantiated at and, for LM_HIP_FAMILY_C32, its slot (0 store with byte symbol loads,
+ * 1 fused argmax, 2 fused threshold, 3 store with dword symbol loads, 4 store + block maxima, 5 continue in place, 6 store at
+ * 16 columns, 7 store + tracked maximum; 0 for every other family). */
+typedef struct lm_hip_registry_row {
+    int family, wide, m, slot;
+    unsigned long long value; /* lm_hip_ctx_launch_tally: launches; lm_hip_registry_rows: equal for rows that share one kernel */
+} lm_hip_registry_row;
+#define LM_HIP_FAMILY_C32 0          /* exact f32 kernels, score_c32<M, MODE> */
+#define LM_HIP_FAMILY_PRE 1          /* one-symbol prefilter scan */
+#define LM_HIP_FAMILY_PREBLK 2       /* ... on 4-row symbol blocks (protein) */
+#define LM_HIP_FAMILY_PRE2 3         /* DNA pair scan */
+#define LM_HIP_FAMILY_PRE2_PROTEIN 4 /* pair scan over the 441 residue pairs */
+#define LM_HIP_FAMILY_PRE2_MULTI 5   /* DNA pair scan, several motifs per pass */
+#define LM_HIP_FAMILY_U8 6           /* u8 scores of a DiscreteMatrix, one symbol per lookup */
+#define LM_HIP_FAMILY_U8_PAIRS 7     /* ... two symbols per lookup (DNA) */
+#define LM_HIP_FAMILY_BEST_FUSED 8   /* best hit per record of a sequence set */
+/* Diagnostic: every row the build registered (the non-null cells of the registry's tables and of the table of
+ * lm_hip_scan_best_seqset, read from the tables themselves).  Writes at most `cap` rows, *count = the number there are.  Host
+ * only: needs no device. */
+int lm_hip_registry_rows(lm_hip_registry_row *rows, size_t cap, size_t *count);
+/* Diagnostic: with the context option "tally_launches" = 1, the registry rows this context has LAUNCHED since the last call
+ * (counted where a kernel is enqueued, not where a row is looked up), `value` = launches.  Writes at most `cap` rows,
+ * *count = the number there are; the tally is cleared when all of them fit (cap >= *count).  Option off: *count = 0. */
+int lm_hip_ctx_launch_tally(lm_hip_ctx *ctx, lm_hip_registry_row *rows, size_t cap, size_t *count);
 
 /* ---- PSSM ---------------------------------------------------------------- */
 

@@ -31,6 +31,15 @@ class SetBest(C.Structure):
     _fields_ = [("position", C.c_uint64), ("score", C.c_float), ("found", C.c_int32)]
 
 
+class RegistryRow(C.Structure):
+    _fields_ = [("family", C.c_int), ("wide", C.c_int), ("m", C.c_int), ("slot", C.c_int), ("value", C.c_ulonglong)]
+
+
+# lm_hip_registry_row::family (LM_HIP_FAMILY_*) and the slots of the c32 family, in the header's order
+FAMILIES = ("c32", "pre", "preblk", "pre2", "pre2_protein", "pre2_multi", "u8", "u8_pairs", "best_fused")
+SLOTS = ("STORE", "ARGMAX", "THRESHOLD", "STORE_QL", "STORE_ARGMAX", "CONTINUE", "STORE_C16", "STORE_TRACK")
+
+
 class LightmotifHipError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"lightmotif_hip error {status}: {message}")
@@ -79,6 +88,8 @@ SIGNATURES = {
     "lm_hip_ctx_last_scan_kernel_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "lm_hip_ctx_last_phases_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "lm_hip_ctx_last_scan_info": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "lm_hip_registry_rows": (C.c_int, [C.POINTER(RegistryRow), _sz, _szp]),
+    "lm_hip_ctx_launch_tally": (C.c_int, [_vp, C.POINTER(RegistryRow), _sz, _szp]),
     "lm_hip_pssm_create": (C.c_int, [_vp, _vp, _sz, _sz, _sz, C.POINTER(_vp)]),
     "lm_hip_pssm_reverse_complement": (C.c_int, [_vp, _vp, C.POINTER(_vp)]),
     "lm_hip_pssm_destroy": (C.c_int, [_vp]),

@@ -354,7 +354,7 @@ int lm_hip_device_clock_mhz(int device, unsigned window_us, double *mhz)
 static const char *const kOptionNames[] = {"track_argmax", "xlong_store", "host_fold", "speculate_order", "suffix_argmax",
                                            "multi_motif", "quad_loads", "skip_unreachable", "pair_prefilter",
                                            "pair_prefilter_protein", "chunked_fused", "chunk_rows", "tiled",
-                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done", "count_tile_rows"};
+                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done", "count_tile_rows", "tally_launches", "track_fold_cells"};
 
 static int set_option(lm_hip_ctx *ctx, const char *name, double value)
 {
@@ -389,6 +389,13 @@ static int set_option(lm_hip_ctx *ctx, const char *name, double value)
         if (!(value >= 0) || !(value <= 65536.0))
             return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: count_tile_rows must be 0 ... 65536");
         ctx->count_tile_rows = (size_t)value;
+    } else if (n == "tally_launches") {  // 1 = count the registry rows launched (lm_hip_ctx_launch_tally)
+        ctx->tally_launches = on;
+        ctx->tally.clear();
+    } else if (n == "track_fold_cells") {  // score_into on handles: cells from which the tracked store folds block maxima in launches of their own; 0 = always
+        if (!(value >= 0) || !(value <= 4294967296.0))
+            return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: track_fold_cells must be 0 ... 2^32");
+        ctx->track_fold_cells = (size_t)value;
     } else if (n == "suffix_occurrences") {
         ctx->suffix_occurrences = value > 0 ? value : 0;
     } else {
@@ -596,6 +603,23 @@ int lm_hip_ctx_last_scan_info(lm_hip_ctx *ctx, size_t *motif_rows_scanned, size_
         *motif_rows_scanned = ctx->last_scan_rows;
     if (lds_bytes_per_position)
         *lds_bytes_per_position = ctx->last_scan_lds_bytes;
+    return LM_HIP_OK;
+}
+
+int lm_hip_ctx_launch_tally(lm_hip_ctx *ctx, lm_hip_registry_row *rows, size_t cap, size_t *count)
+{
+    if (!ctx || !count || (cap && !rows))
+        return fail(LM_HIP_ERR_BAD_ARGS, "ctx_launch_tally: null argument");
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    *count = ctx->tally.size();
+    size_t i = 0;
+    for (const auto &kv : ctx->tally) {
+        if (i == cap)
+            return LM_HIP_OK;  // the caller asks again with room for *count rows
+        rows[i++] = lm_hip_registry_row{(int)(kv.first >> 24), (int)(kv.first >> 16 & 0xff), (int)(kv.first >> 8 & 0xff),
+                                        (int)(kv.first & 0xff), kv.second};
+    }
+    ctx->tally.clear();
     return LM_HIP_OK;
 }
 

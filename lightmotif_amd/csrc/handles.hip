@@ -594,7 +594,7 @@ int lm::score_store_tracked(lm_hip_ctx *ctx, const ScoreArgs &a, lm_hip_scores *
     if (!scores->d_best || !ctx->track_argmax)
         return launch_score_store(ctx, a);
     bool tracked = false;
-    if ((row_end - row_begin) * a.cols < (8u << 20)) {
+    if ((row_end - row_begin) * a.cols < ctx->track_fold_cells) {
         // small inputs are launch-latency bound: ONE launch stores, tracks the best cell and folds the
         // workgroup records (MODE_STORE_TRACK), and leaves the record in pinned memory as well
         const unsigned gen = next_generation(scores->best_generation);

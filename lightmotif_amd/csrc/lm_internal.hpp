@@ -5,6 +5,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <map>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -216,7 +217,21 @@ struct lm_hip_ctx {
     // matrix block after block); `u8_key` = {m, k, pairs} + the weights they were built from
     lm::Scratch u8_tables;
     std::vector<uint8_t> u8_key;
+    size_t track_fold_cells = 8u << 20;  // score_into + tracked maximum: one launch below, block maxima + reductions from here on (option "track_fold_cells")
+    // option "tally_launches": registry rows launched since lm_hip_ctx_launch_tally last read them (lm::tally_launch),
+    // key = family << 24 | wide << 16 | M << 8 | slot
+    bool tally_launches = false;
+    std::map<unsigned, unsigned long long> tally;
 };
+
+namespace lm {
+// at every place a launcher out of the kernel registry (score_registry.hpp) or the fused table of seqset_best.hip is called
+inline void tally_launch(lm_hip_ctx *ctx, int family, bool wide, size_t m, int slot = 0)
+{
+    if (ctx->tally_launches)
+        ++ctx->tally[(unsigned)family << 24 | (unsigned)wide << 16 | (unsigned)m << 8 | (unsigned)slot];
+}
+}  // namespace lm
 
 namespace lm {
 // Region `r` of the staging block as T* for `count` elements that start `byte_off` bytes into it; nullptr: they do not fit.

@@ -32,13 +32,64 @@ static void find_hole()
         if (!filled && !g_hole[0])
             snprintf(g_hole, sizeof g_hole, "kernel registry: no %s kernel for M = %d (a unit of the build is not registered)", row, m);
     };
-    for (int m = 1; m <= kMaxStoreM; ++m)
-        if (m <= kMaxFastM || (m <= kMaxLongM ? m % 4 == 0 : m % 8 == 0))
-            check(g_c32[m][SLOT_STORE] && g_c32w[m][SLOT_STORE], "store", m);
+    static const char *const slot_names[kRegistrySlots] = {"store", "fused argmax", "fused threshold", "dword-load store",
+                                                           "store + block maxima", "continue", "16-column store", "tracked store"};
+    for (int m = 1; m <= kMaxStoreM; ++m) {
+        const bool fast = m <= kMaxFastM, lng = !fast && m <= kMaxLongM && m % 4 == 0, xlong = m > kMaxLongM && m % 8 == 0;
+        if (!fast && !lng && !xlong)
+            continue;
+        for (int slot = 0; slot < kRegistrySlots; ++slot) {
+            const bool quad = slot == SLOT_STORE_QL || slot == SLOT_STORE_TRACK;  // the members that need M % 4 == 0
+            const bool promised = xlong ? (slot == SLOT_STORE || slot == SLOT_STORE_QL)
+                                  : slot == SLOT_STORE_C16 ? fast && m % 4 == 0
+                                  : quad ? m % 4 == 0
+                                         : true;
+            if (promised)
+                check(g_c32[m][slot] && g_c32w[m][slot], slot_names[slot], m);
+        }
+    }
     for (int m = 2; m <= kMaxPairM; ++m)
         check(g_pre2[m], "pair scan", m);
-    for (int m = 1; m <= kMaxFastM; ++m)
-        check(g_pre[m] && g_prew[m] && g_u8[m] && g_u8w[m], "one-symbol scan or u8", m);
+    for (int m = 1; m <= kMaxFastM; ++m) {
+        check(g_pre[m] && g_prew[m], "one-symbol scan", m);
+        check(g_preblk[m], "block scan", m);
+        check(g_u8[m] && g_u8w[m], "u8", m);
+        if (m >= 2) {  // (the pair kernels start at two rows)
+            check(g_pre2_protein[m], "protein pair scan", m);
+            check(g_u8_pairs[m], "u8 pair", m);
+            if (prefilter2_multi(m) > 1)
+                check(g_pre2_multi[m], "multi-motif pair scan", m);
+        }
+        check(seqset_best_fused_row(m), "best-hit", m);
+    }
+}
+
+// every non-null cell of the tables above and of seqset_best.hip's, in table order (lm_hip_registry_rows)
+static std::vector<lm_hip_registry_row> registered_rows()
+{
+    std::vector<lm_hip_registry_row> rows;
+    auto put = [&](int family, int wide, int m, int slot, const void *fn) {
+        if (fn)
+            rows.push_back(lm_hip_registry_row{family, wide, m, slot, (unsigned long long)reinterpret_cast<uintptr_t>(fn)});
+    };
+    for (int wide = 0; wide < 2; ++wide)
+        for (int m = 0; m <= kMaxStoreM; ++m)
+            for (int slot = 0; slot < kRegistrySlots; ++slot)
+                put(LM_HIP_FAMILY_C32, wide, m, slot, reinterpret_cast<const void *>((wide ? g_c32w : g_c32)[m][slot]));
+    for (int m = 0; m <= kMaxPairM; ++m)
+        put(LM_HIP_FAMILY_PRE2, 0, m, 0, reinterpret_cast<const void *>(g_pre2[m]));
+    for (int m = 0; m <= kMaxFastM; ++m) {
+        put(LM_HIP_FAMILY_PRE, 0, m, 0, reinterpret_cast<const void *>(g_pre[m]));
+        put(LM_HIP_FAMILY_PRE, 1, m, 0, reinterpret_cast<const void *>(g_prew[m]));
+        put(LM_HIP_FAMILY_PREBLK, 1, m, 0, reinterpret_cast<const void *>(g_preblk[m]));
+        put(LM_HIP_FAMILY_PRE2_PROTEIN, 1, m, 0, reinterpret_cast<const void *>(g_pre2_protein[m]));
+        put(LM_HIP_FAMILY_PRE2_MULTI, 0, m, 0, reinterpret_cast<const void *>(g_pre2_multi[m]));
+        put(LM_HIP_FAMILY_U8, 0, m, 0, reinterpret_cast<const void *>(g_u8[m]));
+        put(LM_HIP_FAMILY_U8, 1, m, 0, reinterpret_cast<const void *>(g_u8w[m]));
+        put(LM_HIP_FAMILY_U8_PAIRS, 0, m, 0, reinterpret_cast<const void *>(g_u8_pairs[m]));
+        put(LM_HIP_FAMILY_BEST_FUSED, 0, m, 0, seqset_best_fused_row(m));
+    }
+    return rows;
 }
 
 static void init_registry()
@@ -96,6 +147,21 @@ ScoreU8Launcher score_c32_lookup_u8(int M, bool pairs, bool wide)
         return nullptr;
     return pairs ? g_u8_pairs[M] : wide ? g_u8w[M] : g_u8[M];
 }
+
+}  // namespace lm
+
+extern "C" int lm_hip_registry_rows(lm_hip_registry_row *rows, size_t cap, size_t *count)
+{
+    if (!count || (cap && !rows))
+        return lm::fail(LM_HIP_ERR_BAD_ARGS, "registry_rows: null argument");
+    std::call_once(lm::g_c32_once, lm::init_registry);
+    const std::vector<lm_hip_registry_row> all = lm::registered_rows();
+    *count = all.size();
+    std::copy(all.begin(), all.begin() + std::min(cap, all.size()), rows);
+    return LM_HIP_OK;
+}
+
+namespace lm {
 
 const char *score_c32_name(int M, int mode)
 {
@@ -289,6 +355,8 @@ int launch_prefilter_scan(lm_hip_ctx *ctx, int kind, size_t m, size_t k, bool bl
     PrefilterLauncher fn = pairs ? score_c32_prefilter2_lookup((int)m, (int)k) : score_c32_prefilter_lookup((int)m, lds_wide((int)k), blocks);
     if (!fn)
         return fail(LM_HIP_ERR_HIP, "no %s kernel for M = %zu, K = %zu", ctx->last_kernel, m, k);
+    tally_launch(ctx, pairs ? (k == 5 ? LM_HIP_FAMILY_PRE2 : LM_HIP_FAMILY_PRE2_PROTEIN) : blocks ? LM_HIP_FAMILY_PREBLK : LM_HIP_FAMILY_PRE,
+                 lds_wide((int)k), m);
     LM_HIP_TRY(fn(plan.grid, plan.lds, st, d_seq, image, (int)k, row_begin, row_end, plan.T, plan.nstreams, td, fo));
     return LM_HIP_OK;
 }
@@ -302,6 +370,7 @@ int launch_group_scan(lm_hip_ctx *ctx, const ScanPlan &sp, size_t gi, const JobG
         dim3 grid = g.plan.grid;
         grid.y = (unsigned)((g.idx.size() + sg.per_pass - 1) / sg.per_pass);
         ctx->last_kernel = "score_c32_prefilter2_multi";
+        tally_launch(ctx, LM_HIP_FAMILY_PRE2_MULTI, false, p->m);
         LM_HIP_TRY(score_c32_prefilter2_multi_lookup((int)p->m)(grid, st, a.d_seq, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams, fo));
         return LM_HIP_OK;
     }
@@ -320,6 +389,7 @@ int launch_group_scan(lm_hip_ctx *ctx, const ScanPlan &sp, size_t gi, const JobG
     ctx->last_kernel = score_c32_name((int)em.m, mode);
     if (!fn)
         return fail(LM_HIP_ERR_HIP, "no %s kernel", ctx->last_kernel);
+    tally_launch(ctx, LM_HIP_FAMILY_C32, lds_wide((int)p->k), em.m, mode);
     LM_HIP_TRY(fn(g.plan.grid, g.plan.lds, st, a.d_seq, em.table, (int)p->k, a.row_begin, a.row_end, g.plan.T, g.plan.nstreams,
                   nullptr, efo));
     return LM_HIP_OK;

@@ -64,6 +64,7 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
         if (pp.ok && pfn) {
             fo.lead_rows = (unsigned)a.pssm->lead;
             ctx->last_kernel = score_c32_name((int)mp, MODE_STORE);
+            tally_launch(ctx, LM_HIP_FAMILY_C32, wide, mp, a.cols == 16 ? SLOT_STORE_C16 : SLOT_STORE_QL);
             LM_HIP_TRY(pfn(pp.grid, pp.lds, ctx->stream, a.d_seq, a.pssm->d_table_pad,
                                                     (int)a.pssm->k, a.row_begin, a.row_end, pp.T, pp.nstreams, a.d_out,
                                                     fo));
@@ -75,12 +76,14 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
                                                                   store_rows_hint(a.pssm->m, a.cols), c16)
                                                       : C32Plan{};  // longer: the slices below
     if (p.ok) {
-        ScoreC32Launcher fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE, wide);
+        int slot = SLOT_STORE;
         if (dwords && score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide))
-            fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide);  // dword symbol loads (M % 4 == 0)
+            slot = SLOT_STORE_QL;  // dword symbol loads (M % 4 == 0)
         if (c16)
-            fn = score_c32_lookup((int)a.pssm->m, SLOT_STORE_C16, wide);  // four streams of 16 columns per wavefront
+            slot = SLOT_STORE_C16;  // four streams of 16 columns per wavefront
+        ScoreC32Launcher fn = score_c32_lookup((int)a.pssm->m, slot, wide);
         ctx->last_kernel = score_c32_name((int)a.pssm->m, MODE_STORE);
+        tally_launch(ctx, LM_HIP_FAMILY_C32, wide, a.pssm->m, slot);
         LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, a.pssm->d_table, (int)a.pssm->k,
                       a.row_begin, a.row_end, p.T, p.nstreams, a.d_out, fo));
         return LM_HIP_OK;
@@ -107,8 +110,10 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             pfo.lead_rows = (unsigned)part.lead;
             if (i == 0) {
                 ScoreC32Launcher fn = score_c32_lookup((int)part.m, SLOT_STORE_QL, wide);
+                const int slot = fn ? SLOT_STORE_QL : SLOT_STORE;
                 if (!fn)
                     fn = score_c32_lookup((int)part.m, SLOT_STORE, wide);
+                tally_launch(ctx, LM_HIP_FAMILY_C32, wide, part.m, slot);
                 LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, sa.d_seq, part.d_table, (int)a.pssm->k, a.row_begin, a.row_end,
                               p.T, p.nstreams, a.d_out, pfo));
                 continue;
@@ -116,6 +121,7 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             const unsigned long long nfull = n / p.T;
             if (nfull) {
                 const dim3 grid((unsigned)((nfull + kStreamsPerBlock - 1) / kStreamsPerBlock));
+                tally_launch(ctx, LM_HIP_FAMILY_C32, wide, part.m, SLOT_CONTINUE);
                 LM_HIP_TRY(score_c32_lookup((int)part.m, SLOT_CONTINUE, wide)(grid, p.lds, ctx->stream, sa.d_seq, part.d_table,
                                                                   (int)a.pssm->k, a.row_begin, a.row_begin + nfull * p.T,
                                                                   p.T, nfull, a.d_out, pfo));
@@ -290,6 +296,7 @@ int launch_score_u8(lm_hip_ctx *ctx, const DiscreteArgs &a)
     char *dev = static_cast<char *>(ctx->u8_tables.ptr);
     if (fn) {
         ctx->last_kernel = pairs ? "score_c32_u8_pairs" : "score_c32_u8";
+        tally_launch(ctx, pairs ? LM_HIP_FAMILY_U8_PAIRS : LM_HIP_FAMILY_U8, !pairs && lds_wide(k), a.m);
         LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, reinterpret_cast<const unsigned *>(dev), k, a.row_begin,
                       a.row_end, p.T, p.nstreams, a.d_out, wrap_mask));
         return LM_HIP_OK;
@@ -419,6 +426,7 @@ int launch_score_store_argmax(lm_hip_ctx *ctx, const ScoreArgs &a, ArgmaxRecord 
     ArgmaxRecord *folded = fo.block_best + nrec;
     fo.lead_rows = pad ? lead : 0u;
     ctx->last_kernel = score_c32_name((int)mk, MODE_STORE);
+    tally_launch(ctx, LM_HIP_FAMILY_C32, lds_wide((int)a.pssm->k), mk, SLOT_STORE_ARGMAX);
     LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, pad ? pad_table : a.pssm->d_table, (int)a.pssm->k,
                   a.row_begin, a.row_end, p.T, p.nstreams, a.d_out, fo));
     const ArgmaxRecord *recs = fo.block_best;
@@ -576,6 +584,7 @@ int launch_score_store_track(lm_hip_ctx *ctx, const ScoreArgs &a, ArgmaxRecord *
     fo.generation = generation;
     fo.first_cell_rule = first_cell_rule;
     ctx->last_kernel = score_c32_name((int)mk, MODE_STORE);
+    tally_launch(ctx, LM_HIP_FAMILY_C32, lds_wide((int)a.pssm->k), mk, SLOT_STORE_TRACK);
     LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, table, (int)a.pssm->k, a.row_begin, a.row_end, p.T, p.nstreams,
                   a.d_out, fo));
     if (on_host) {

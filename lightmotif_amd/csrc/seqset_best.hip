@@ -320,6 +320,11 @@ constexpr size_t kBestBlockBytes = (size_t)256 << 20;  // slots + results of one
 }  // namespace best
 using namespace best;
 
+const void *seqset_best_fused_row(int M)
+{
+    return (M >= 1 && M <= kMaxFastM) ? reinterpret_cast<const void *>(fused().fn[M]) : nullptr;
+}
+
 // Rows per lane: long enough that the M - 1 fill steps of a run cost little, short enough that the `njobs` jobs of the
 // call put a few wavefronts on every SIMD.
 static unsigned long long best_rows_per_lane(const lm_hip_ctx *ctx, const lm_hip_seq *seq, size_t m, size_t njobs)
@@ -389,6 +394,7 @@ int launch_seqset_best(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const c
             hipStream_t st = streams.next();
             if (g.kind == KIND_EXACT) {
                 const size_t lds = (((size_t)p->k * table_stride((int)p->m, 0) * 4 + 15) & ~(size_t)15) + off_bytes;
+                tally_launch(ctx, LM_HIP_FAMILY_BEST_FUSED, false, p->m);
                 hipLaunchKernelGGL(fused().fn[p->m], grid, dim3(kBlock), lds, st, seq->d_data, (unsigned long long)seq->stride,
                                    (unsigned)seq->cols, (unsigned long long)seq->rows, (unsigned long long)(seq->rows + seq->wrap),
                                    (unsigned)p->k, d_jobs + first[gi], set->d_offsets, (unsigned long long)records, (int)off_lds, T,

@@ -151,6 +151,26 @@ class Pipeline:
     def last_kernel(self) -> str:
         return self._L.lm_hip_ctx_last_kernel(self._h).decode()
 
+    @staticmethod
+    def _registry_rows(call) -> Dict[Tuple[str, int, int, str], int]:
+        n = C.c_size_t(0)
+        check(call(None, 0, C.byref(n)))
+        rows = (_ffi.RegistryRow * max(n.value, 1))()
+        check(call(rows, n.value, C.byref(n)))
+        return {(_ffi.FAMILIES[r.family], r.wide, r.m, _ffi.SLOTS[r.slot] if r.family == 0 else ""): int(r.value)
+                for r in rows[:n.value]}
+
+    @staticmethod
+    def registry_rows() -> Dict[Tuple[str, int, int, str], int]:
+        """Every kernel row the build registered, ``(family, wide, M, slot) -> id`` (lm_hip_registry_rows): rows with
+        equal ids share one kernel; ``slot`` is "" outside the "c32" family.  Needs no device."""
+        return Pipeline._registry_rows(_ffi.lib().lm_hip_registry_rows)
+
+    def launch_tally(self) -> Dict[Tuple[str, int, int, str], int]:
+        """With ``set_option("tally_launches", 1)``: the registry rows this pipeline launched since the last call,
+        ``(family, wide, M, slot) -> launches``; reading clears the tally (lm_hip_ctx_launch_tally)."""
+        return Pipeline._registry_rows(lambda rows, cap, n: self._L.lm_hip_ctx_launch_tally(self._h, rows, cap, n))
+
     @property
     def last_scan_counts(self) -> Tuple[int, int]:
         """(hits, candidate pieces) of the last fused threshold scan on this pipeline (lm_hip_ctx_last_scan_counts)."""

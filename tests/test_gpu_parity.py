@@ -326,7 +326,7 @@ def test_generated_fixtures(pli, name):
         assert np.array_equal(got, c[f"threshold_{i}"])
 
 
-@pytest.mark.parametrize("m", list(range(1, 35)) + [40, 64])
+@pytest.mark.parametrize("m", list(range(1, 37)) + [40, 64])
 def test_every_motif_length_dna(pli, m):
     """Unrolled kernels exist for M = 1..36; longer motifs take the generic kernel."""
     rng = np.random.default_rng(1000 + m)
