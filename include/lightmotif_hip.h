@@ -173,6 +173,8 @@ int lm_hip_ctx_set_track_argmax(lm_hip_ctx *ctx, int enabled);
  * memory instead of waiting for its stream: 3-4 us less per call, unless the caller synchronises the device right behind it),
  * "count_tile_rows" (rows per block of the table behind lm_hip_seq_count_symbols / lm_hip_seqset_count_symbols, 1 ... 65536;
  * 0 = the default of 1024: a small value makes a small input span many blocks of the table and of its scan),
+ * "site_chunk" (most sites per chunk of lm_hip_seqset_windows / lm_hip_seqset_count_sites, 0 = the default: a small value
+ * makes a small list cross chunk boundaries),
  * "tally_launches" (1 = count the registry rows launched, lm_hip_ctx_launch_tally), "track_fold_cells" (score_into on handles
  * stores + tracks the maximum in ONE launch below this many cells and with block maxima + two reduction launches from it on;
  * default 8 Mi, 0 = always the latter: lets a small input take the large inputs' route); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
@@ -516,6 +518,46 @@ int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, si
  * 0.25 for protein) and 16 k bytes per record.  The pass reads 1 byte per position. */
 int lm_hip_seq_count_symbols(lm_hip_ctx *ctx, const lm_hip_seq *seq, uint64_t *counts, size_t capacity);
 int lm_hip_seqset_count_symbols(lm_hip_ctx *ctx, const lm_hip_seqset *set, uint64_t *counts, size_t capacity);
+
+/* Symbols read back OUT of a resident set (csrc/sites.hip): the text of hit windows -- FIMO's `matched_sequence` -- the
+ * count matrix of a motif's sites, whole records.  A set built from FASTA bytes never passed through the host, so these
+ * are the only way to see what a hit matched without parsing the file a second time.
+ *   sites       n motifs in caller order; counts[i] CONSECUTIVE sites belong to motif i.  The sites lie
+ *               `site_stride_bytes` (>= 16) apart, each a `size_t record` at +0 and a `size_t position` at +8: the
+ *               lm_hip_set_hit list of lm_hip_scan_threshold_seqset passes as it is with sizeof(lm_hip_set_hit) = 24,
+ *               packed (record, position) pairs with 16.
+ *   windows     a site names the window [position + shifts[i], position + shifts[i] + widths[i]) of its record;
+ *               widths[i] >= 1, shifts may be NULL (all zero).  It is VALID when record < records, position + shift >= 0
+ *               and position + shift + width <= the record's own length, evaluated without wrap-around for every 64-bit
+ *               position and shift: a window never leaves its record.  An invalid site is not an error.
+ *   reads       symbol q of the concatenation sits at row q % rows, column q / rows (pli/mod.rs:178-200), which is
+ *               StripedSequence's Index (seq.rs:433-442); wrap rows are never read, so the result is the same before and
+ *               after lm_hip_seqset_configure_wrap.
+ * lm_hip_seqset_windows writes the widths[i] symbol bytes (indices < k, not ASCII) of every site, motif-major and then
+ * in site order: sum(counts[i] * widths[i]) bytes; invalid sites read 0xFF.  valid (may be NULL) receives one byte per
+ * site, 1 or 0.  One site per record with width = the record's length reads whole records back.
+ * lm_hip_seqset_count_sites is CountMatrix::from_sequences (pwm/mod.rs:209-237) over the windows of each motif's valid
+ * sites -- the motif table the Gibbs sampler builds from its start positions (sampler.rs:412-422) -- without the windows
+ * leaving the device: tables holds k * sum(widths) entries, motif-major and then row-major, table_i[j][s] = the number of
+ * valid sites of motif i whose j-th symbol is s; used (n entries, may be NULL) the number of valid sites, which is what
+ * every row of table_i sums to.  For the sites of a reverse-complemented matrix the table of the forward motif is
+ * CountMatrix::reverse_complement of the result (pwm/mod.rs:313-321: rows reversed, columns swapped), a host matter.
+ * `capacity` is in elements (bytes / table entries): LM_HIP_ERR_CAPACITY when it is short, and nothing is written.
+ * LM_HIP_ERR_BAD_ARGS, before any device work: null arguments (with n > 0: counts, widths, sites and the output), a width
+ * of 0, a stride below 16, a set that lives on another device than the context.  n == 0 or no sites at all: LM_HIP_OK,
+ * tables zero-filled, nothing launched.  Every position and count is 64-bit; integer adds commute, so a call repeats
+ * byte for byte.  Both calls enqueue on the context's stream and synchronise it; lm_hip_ctx_last_kernel then names
+ * "site_windows", or "site_counts_lds" (a workgroup counts a slice of one motif's sites in a private LDS table and adds
+ * its non-zero counters with one 64-bit atomic each) or "site_counts_direct" (width * k beyond 12 287 counters: every
+ * symbol adds to global memory).  TEMPORARY DEVICE MEMORY: sites are uploaded and processed in chunks of at most 256 MB of
+ * sites (16 bytes each) plus, for the windows, their bytes -- a single window may exceed that on its own; the option
+ * "site_chunk" caps the sites per chunk.  Motifs without sites or wider than the whole set never reach the device. */
+int lm_hip_seqset_windows(lm_hip_ctx *ctx, const lm_hip_seqset *set, const size_t *counts, const size_t *widths,
+                          const int64_t *shifts, size_t n, const void *sites, size_t site_stride_bytes,
+                          uint8_t *symbols, size_t capacity, uint8_t *valid /* may be NULL */);
+int lm_hip_seqset_count_sites(lm_hip_ctx *ctx, const lm_hip_seqset *set, const size_t *counts, const size_t *widths,
+                              const int64_t *shifts, size_t n, const void *sites, size_t site_stride_bytes,
+                              uint64_t *tables, size_t capacity, uint64_t *used /* n entries, may be NULL */);
 
 /* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
  * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the

@@ -127,6 +127,8 @@ SIGNATURES = {
     "lm_hip_scan_best_seqset": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, C.POINTER(SetBest)]),
     "lm_hip_seq_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
+    "lm_hip_seqset_windows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "lm_hip_seqset_count_sites": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "lm_hip_dists_create": (C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     "lm_hip_dists_len": (_sz, [_vp]),
     "lm_hip_dists_info": (C.c_int, [_vp, _sz, _szp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _szp]),

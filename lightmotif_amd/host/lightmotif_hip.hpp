@@ -251,9 +251,88 @@ public:
         check(lm_hip_seqset_count_symbols(ctx_->ctx, h_, out.empty() ? &none : out.data(), out.size()));
         return out;
     }
+    // Symbols read back out of the set (csrc/sites.hip).  A site names the window [position + shift, position + shift + width)
+    // of its record; one that does not lie inside the record is invalid: its bytes read 0xFF and it counts nowhere.
+    struct Site {
+        size_t record, position;
+    };
+    // per motif: the windows end to end (sites[i].size() * widths[i] symbol indices) and one validity byte per site
+    struct SiteWindows {
+        std::vector<uint8_t> symbols, valid;
+    };
+    std::vector<SiteWindows> windows(const std::vector<std::vector<Site>> &sites, const std::vector<size_t> &widths,
+                                     const std::vector<int64_t> &shifts = {}) const
+    {
+        const SiteArgs a(sites, widths, shifts);
+        std::vector<uint8_t> symbols(a.bytes + 1), valid(a.flat.size() + 1);
+        check(lm_hip_seqset_windows(ctx_->ctx, h_, a.counts.data(), widths.data(), a.shifts(), sites.size(), a.flat.data(), sizeof(Site),
+                                    symbols.data(), a.bytes, valid.data()));
+        std::vector<SiteWindows> out(sites.size());
+        size_t b = 0, v = 0;
+        for (size_t i = 0; i < sites.size(); ++i) {
+            const size_t nb = sites[i].size() * widths[i];
+            out[i].symbols.assign(symbols.begin() + b, symbols.begin() + b + nb);
+            out[i].valid.assign(valid.begin() + v, valid.begin() + v + sites[i].size());
+            b += nb, v += sites[i].size();
+        }
+        return out;
+    }
+    // CountMatrix::from_sequences (pwm/mod.rs:209-237) over the windows of each motif's valid sites, counted on the device:
+    // tables[i] is widths[i] x A::K, row-major (CountMatrix<A>::from_table makes the matrix), used[i] the valid sites
+    struct SiteCounts {
+        std::vector<std::vector<uint64_t>> tables;
+        std::vector<uint64_t> used;
+    };
+    SiteCounts count_sites(const std::vector<std::vector<Site>> &sites, const std::vector<size_t> &widths,
+                           const std::vector<int64_t> &shifts = {}) const
+    {
+        const SiteArgs a(sites, widths, shifts);
+        size_t entries = 0;
+        for (size_t w : widths)
+            entries += w * A::K;
+        std::vector<uint64_t> flat(entries + 1);
+        SiteCounts out;
+        out.used.resize(sites.size() + 1);
+        check(lm_hip_seqset_count_sites(ctx_->ctx, h_, a.counts.data(), widths.data(), a.shifts(), sites.size(), a.flat.data(), sizeof(Site),
+                                        flat.data(), entries, out.used.data()));
+        out.used.resize(sites.size());
+        size_t at = 0;
+        for (size_t w : widths) {
+            out.tables.emplace_back(flat.begin() + at, flat.begin() + at + w * A::K);
+            at += w * A::K;
+        }
+        return out;
+    }
+    // Record r read back (StripedSequence's Index, seq.rs:433-442, position by position)
+    EncodedSequence<A> record(size_t r) const
+    {
+        const size_t n = len(r);
+        if (n == 0)
+            return EncodedSequence<A>(std::vector<uint8_t>());
+        return EncodedSequence<A>(std::move(windows({{Site{r, 0}}}, {n})[0].symbols));
+    }
     lm_hip_seqset *handle() const { return h_; }
 
 private:
+    struct SiteArgs {
+        std::vector<size_t> counts;
+        std::vector<Site> flat;
+        const std::vector<int64_t> &shift;
+        size_t bytes = 0;
+        SiteArgs(const std::vector<std::vector<Site>> &sites, const std::vector<size_t> &widths, const std::vector<int64_t> &s) : shift(s)
+        {
+            if (widths.size() != sites.size() || (!s.empty() && s.size() != sites.size()))
+                throw std::invalid_argument("one width (and one shift) per motif");
+            for (size_t i = 0; i < sites.size(); ++i) {
+                counts.push_back(sites[i].size());
+                flat.insert(flat.end(), sites[i].begin(), sites[i].end());
+                bytes += sites[i].size() * widths[i];
+            }
+            counts.push_back(0);     // (never empty: an empty call still hands pointers over)
+            flat.push_back(Site{0, 0});
+        }
+        const int64_t *shifts() const { return shift.empty() ? nullptr : shift.data(); }
+    };
     struct Info { size_t records, total, rows, wrap, cols, k; };
     Info info() const
     {
@@ -548,6 +627,30 @@ public:
                 d(i, s.data[i]) += 1;
         }
         return CountMatrix(std::move(d));
+    }
+    // a width x A::K table of SequenceSet::count_sites; std::overflow_error when a count exceeds the matrix's u32
+    static CountMatrix from_table(const std::vector<uint64_t> &table)
+    {
+        if (table.size() % A::K)
+            throw InvalidData();
+        DenseMatrix<uint32_t> d(table.size() / A::K, A::K);
+        for (size_t i = 0; i < table.size(); ++i) {
+            if (table[i] > 0xFFFFFFFFull)
+                throw std::overflow_error("a site count exceeds u32");
+            d(i / A::K, i % A::K) = (uint32_t)table[i];
+        }
+        return CountMatrix(std::move(d));
+    }
+    // pwm/mod.rs:313-321 (ComplementableAlphabet = Dna): rows reversed, A<->T and C<->G swapped
+    CountMatrix reverse_complement() const
+    {
+        static_assert(A::K == 5, "only the DNA alphabet has a complement");
+        static const size_t comp[5] = {2, 3, 0, 1, 4};
+        DenseMatrix<uint32_t> out(data.rows(), A::K);
+        for (size_t i = 0; i < data.rows(); ++i)
+            for (size_t s = 0; s < A::K; ++s)
+                out(i, s) = data(data.rows() - 1 - i, comp[s]);
+        return CountMatrix(std::move(out));
     }
     // pwm/mod.rs:240-258 with a scalar pseudocount (abc.rs:558-573)
     FrequencyMatrix<A> to_freq(float pseudo) const

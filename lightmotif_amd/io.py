@@ -1,4 +1,4 @@
-"""JASPAR 2016 ("jaspar16") count-matrix reader -- host-side text parsing that feeds
+"""JASPAR 2016 ("jaspar16") count-matrix reader and writer -- host-side text parsing that feeds
 the GPU path.  Behaviour follows the reference's
 lightmotif-io/src/jaspar16/{mod,parse}.rs:
 
@@ -14,7 +14,7 @@ import gzip
 import os
 import re
 from dataclasses import dataclass
-from typing import Iterator, Optional, TextIO, Union
+from typing import Iterable, Iterator, Optional, TextIO, Union
 
 import numpy as np
 
@@ -84,3 +84,27 @@ def _build(header: str, rows: list, protein: bool) -> Record:
         counts[:, sym.index(letter)] = vals
         done.add(letter)
     return Record(ident, desc, CountMatrix(counts, protein=protein))
+
+
+def write(records: Iterable[Record], file: Union[str, TextIO]) -> None:
+    """Writes records in the JASPAR-2016 format ``read`` parses: a header ``>id`` (tab, description) and one bracketed line
+    of counts per symbol.  The default symbol's line (``N``) is written only when it holds a count: files of the format do not
+    carry it, a missing line reads back as zeros, and the parsers (here and parse.rs:36-78) accept the line when present."""
+    close = False
+    if isinstance(file, (str, os.PathLike)):
+        path = os.fspath(file)
+        file = gzip.open(path, "wt") if path.endswith(".gz") else open(path, "w")
+        close = True
+    try:
+        for rec in records:
+            file.write(f">{rec.id}\t{rec.description}\n" if rec.description else f">{rec.id}\n")
+            sym = _symbols(rec.matrix.protein)
+            data = rec.matrix.data
+            digits = max(1, len(str(int(data.max())))) if data.size else 1
+            for s, letter in enumerate(sym):
+                if s == len(sym) - 1 and not data[:, s].any():
+                    continue
+                file.write(f"{letter}  [ " + " ".join(f"{int(v):>{digits}}" for v in data[:, s]) + " ]\n")
+    finally:
+        if close:
+            file.close()

@@ -27,7 +27,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 __all__ = [
     "pack_2bit", "fasta_names",
     "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "ScoreDistributions", "CountMatrix", "WeightMatrix",
-    "background_from_counts",
+    "background_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -710,6 +710,79 @@ def _count_symbols(call, ctx, handle, records: int, k: int) -> np.ndarray:
     return out.reshape(records, k)
 
 
+def decode(symbols, protein: bool = False) -> str:
+    """Symbol indices (a ``windows`` row, an ``EncodedSequence``) as text; ``ValueError`` for a byte that is no symbol, such
+    as the 0xFF of an invalid window."""
+    data = np.asarray(symbols, dtype=np.uint8).reshape(-1)
+    table = np.frombuffer(_symbols(protein).encode("ascii"), dtype=np.uint8)
+    if data.size and int(data.max()) >= table.size:
+        raise ValueError(f"byte {int(data.max())} is not a symbol index")
+    return table[data].tobytes().decode("ascii")
+
+
+def _u64_array(values) -> np.ndarray:
+    """Record numbers or positions as uint64, whatever integer type they come in (a negative one wraps, and is then invalid)."""
+    a = np.asarray(values)
+    if a.dtype.kind == "f" and not isinstance(values, np.ndarray) and all(isinstance(v, (int, np.integer)) for v in values):
+        a = np.asarray(values, dtype=object)     # (Python ints on both sides of 2^63 become floats otherwise)
+    if a.dtype == object:
+        a = np.array([int(v) % (1 << 64) for v in a.reshape(-1)], dtype=np.uint64)
+    elif a.dtype.kind == "i":
+        a = a.astype(np.int64).view(np.uint64)
+    elif a.dtype.kind == "u" or a.size == 0:
+        a = a.astype(np.uint64)
+    else:
+        raise TypeError("records and positions are integers")
+    if a.ndim != 1:
+        raise ValueError("records and positions are one-dimensional")
+    return a
+
+
+def _site_args(sites, widths, shifts=0):
+    """What ``windows`` / ``count_sites`` hand to the C ABI: ``(counts, widths, shifts, buffer, stride)``.  ``sites`` is a
+    ``SetHits`` (its ``lm_hip_set_hit`` list passes as it is) or, per motif, a pair of (record, position) arrays; ``widths``
+    holds one int or one matrix (its length is the width) per motif, ``shifts`` one int per motif or one for all.
+    ``ValueError`` when the lengths disagree."""
+    if isinstance(sites, SetHits):
+        counts = np.ascontiguousarray(sites.counts, dtype=np.uintp)
+        buf = np.ascontiguousarray(sites.hits)
+        stride_ = buf.dtype.itemsize
+    else:
+        pairs = []
+        for pair in sites:
+            if len(pair) != 2:
+                raise ValueError("a motif's sites are a pair of (record, position) arrays")
+            rec, pos = _u64_array(pair[0]), _u64_array(pair[1])
+            if rec.shape != pos.shape:
+                raise ValueError(f"{rec.size} records against {pos.size} positions")
+            pairs.append((rec, pos))
+        counts = np.array([len(r) for r, _ in pairs], dtype=np.uintp)
+        buf = np.zeros((int(counts.sum()), 2), dtype=np.uint64)
+        if pairs:
+            buf[:, 0] = np.concatenate([r for r, _ in pairs]) if buf.size else 0
+            buf[:, 1] = np.concatenate([q for _, q in pairs]) if buf.size else 0
+        stride_ = 16
+    n = len(counts)
+    if isinstance(widths, (int, np.integer)) or not hasattr(widths, "__iter__"):
+        raise TypeError("widths: one int or one matrix per motif")
+    w = np.array([int(x) if isinstance(x, (int, np.integer)) else len(x) for x in widths], dtype=np.uintp)
+    if len(w) != n:
+        raise ValueError(f"{len(w)} widths for the sites of {n} motifs")
+    if (w == 0).any():
+        raise ValueError("a window holds at least one symbol")
+    if isinstance(shifts, (int, np.integer)):
+        sh = np.full(n, int(shifts), dtype=np.int64)
+    else:
+        sh = np.array([int(x) for x in shifts], dtype=np.int64)
+        if len(sh) != n:
+            raise ValueError(f"{len(sh)} shifts for the sites of {n} motifs")
+    return counts, w, sh, buf, stride_
+
+
+def _ptr(a: np.ndarray) -> int:
+    return a.ctypes.data if a.size else np.zeros(2, dtype=np.uint64).ctypes.data
+
+
 def _symbol_index(symbol: str, protein: bool) -> int:
     i = _symbols(protein).find(symbol) if isinstance(symbol, str) and len(symbol) == 1 else -1
     if i < 0:
@@ -927,6 +1000,84 @@ class StripedSequenceSet:
         """``Background::from_sequences`` (abc.rs:441-456) of the set's records: ``k`` f32 frequencies."""
         return background_from_counts(self.count_symbols(), unknown)
 
+    def windows(self, sites, widths, shifts=0) -> List[Tuple[np.ndarray, np.ndarray]]:
+        """The symbols of the windows ``[position + shift, position + shift + width)`` of the given sites, read out of the
+        resident matrix in one call (``lm_hip_seqset_windows``): per motif a ``(count, width)`` uint8 array of symbol
+        indices and a bool array ``valid``.  A window that does not lie inside its record is invalid and reads 0xFF.
+        ``sites``, ``widths``, ``shifts``: see ``_site_args``."""
+        counts, w, sh, buf, stride_ = _site_args(sites, widths, shifts)
+        if len(counts) == 0:
+            return []
+        out, valid = self._windows(counts, w, sh, buf, stride_)
+        res, a, b = [], 0, 0
+        for c, x in zip(counts.tolist(), w.tolist()):
+            res.append((out[a:a + c * x].reshape(c, x), valid[b:b + c] != 0))
+            a, b = a + c * x, b + c
+        return res
+
+    def _windows(self, counts, w, sh, buf, stride_) -> Tuple[np.ndarray, np.ndarray]:
+        """``lm_hip_seqset_windows`` on normalised arguments: all window bytes end to end, and one byte per site."""
+        total = sum(int(c) * int(x) for c, x in zip(counts.tolist(), w.tolist()))
+        out = np.empty(max(total, 1), dtype=np.uint8)
+        valid = np.empty(max(int(counts.sum()), 1), dtype=np.uint8)
+        keep = _ptr(buf)   # (the pointer of an empty list still has to be one)
+        check(self._pli._L.lm_hip_seqset_windows(self._pli._h, self._h, counts.ctypes.data, w.ctypes.data, sh.ctypes.data, len(counts),
+                                                 buf.ctypes.data if buf.size else keep, stride_, out.ctypes.data, total,
+                                                 valid.ctypes.data))
+        return out[:total], valid[:int(counts.sum())]
+
+    def count_sites(self, sites, widths, shifts=0) -> Tuple[List["CountMatrix"], np.ndarray]:
+        """``CountMatrix::from_sequences`` (pwm/mod.rs:209-237) over the windows of each motif's valid sites, counted on the
+        device without the windows leaving it (``lm_hip_seqset_count_sites``): ``(matrices, used)`` with ``used[i]`` the
+        number of valid sites of motif ``i``, which every row of matrix ``i`` sums to.  ``OverflowError`` when a count
+        exceeds the u32 of a ``CountMatrix``."""
+        counts, w, sh, buf, stride_ = _site_args(sites, widths, shifts)
+        n, k = len(counts), _k(self.protein)
+        if n == 0:
+            return [], np.zeros(0, dtype=np.int64)
+        entries = k * int(w.sum())
+        tables = np.zeros(entries, dtype=np.uint64)
+        used = np.zeros(n, dtype=np.uint64)
+        keep = _ptr(buf)
+        check(self._pli._L.lm_hip_seqset_count_sites(self._pli._h, self._h, counts.ctypes.data, w.ctypes.data, sh.ctypes.data, n,
+                                                     buf.ctypes.data if buf.size else keep, stride_, tables.ctypes.data, entries,
+                                                     used.ctypes.data))
+        if tables.size and int(tables.max()) > 0xFFFFFFFF:
+            raise OverflowError("a site count exceeds the u32 of a CountMatrix")
+        mats, a = [], 0
+        for x in w.tolist():
+            mats.append(CountMatrix(tables[a:a + x * k].reshape(x, k), protein=self.protein))
+            a += x * k
+        return mats, used.astype(np.int64)
+
+    def records(self) -> List["EncodedSequence"]:
+        """Every record read back from the set (``StripedSequence``'s Index, seq.rs:433-442, position by position): one
+        ``windows`` call with one site per non-empty record."""
+        lengths = self.lengths
+        live = np.flatnonzero(lengths > 0)            # (a window holds at least one symbol)
+        sites = np.zeros((len(live), 2), dtype=np.uint64)
+        sites[:, 0] = live
+        if len(live):
+            flat, valid = self._windows(np.ones(len(live), dtype=np.uintp), lengths[live].astype(np.uintp),
+                                        np.zeros(len(live), dtype=np.int64), sites, 16)
+            assert valid.all()
+        else:
+            flat = np.zeros(0, dtype=np.uint8)
+        ends = np.cumsum(lengths)                     # empty records take an empty slice
+        return [EncodedSequence(flat[b - n:b], protein=self.protein) for n, b in zip(lengths.tolist(), ends.tolist())]
+
+    def record(self, r: int) -> "EncodedSequence":
+        """Record ``r`` read back from the set."""
+        n = len(self)
+        if not -n <= r < n:
+            raise IndexError("record index out of range")
+        r %= n
+        length = C.c_size_t(0)
+        check(self._pli._L.lm_hip_seqset_record_length(self._h, r, C.byref(length)))
+        if length.value == 0:
+            return EncodedSequence(np.zeros(0, dtype=np.uint8), protein=self.protein)
+        return EncodedSequence(self.windows([([r], [0])], [length.value])[0][0][0], protein=self.protein)
+
 
 # --- matrices ------------------------------------------------------------------------
 
@@ -968,6 +1119,12 @@ class CountMatrix:
                 raise ValueError("Inconsistent sequence length")
             np.add.at(data, (np.arange(m), s.data), 1)
         return cls(data, protein=protein)
+
+    def reverse_complement(self) -> "CountMatrix":
+        """pwm/mod.rs:313-321: rows reversed, every symbol's column taken from its complement (A<->T, C<->G, N->N)."""
+        if self.protein:
+            raise ValueError("cannot complement a protein matrix")
+        return CountMatrix(self.data[::-1, :5][:, [2, 3, 0, 1, 4]], protein=False)
 
     def __len__(self) -> int:
         return self.data.shape[0]

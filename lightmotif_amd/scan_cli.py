@@ -38,6 +38,12 @@ over the FASTA file (with the chosen ``--ingest``) makes every chunk a resident 
 ``to_freq(0.1).to_scoring(background)`` (pwm/mod.rs:415-430), and thresholds and the ``pvalue`` column come from the
 distributions of THOSE matrices.  The second pass scans as before.  ``--composition PATH`` writes, during the scan pass,
 one TSV line per record: ``seq_index seq_name length`` and one count per symbol in alphabet order (``A C T G N``).
+``--matched`` appends a ninth column ``matched``: the text of the hit's window, reverse-complemented for strand ``-`` (FIMO's
+``matched_sequence``).  ``--site-matrices PATH`` writes one JASPAR-2016 record per motif with the counts over all its hits
+in all sets (``CountMatrix::from_sequences`` of the ``matched`` strings, pwm/mod.rs:209-237); motifs without hits get zeros.
+Both read the windows out of the resident set (``StripedSequenceSet.windows`` / ``count_sites``: one call per set and
+strand; for ``-`` the count table of the reverse matrix's sites is reverse-complemented, pwm/mod.rs:313-321) -- with
+``--ingest device`` the host never held the text -- and with ``--best`` the best windows are the sites.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -52,7 +58,7 @@ from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
 import numpy as np
 
 from . import io as lmio
-from .lib import (DNA_SYMBOLS, MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet, background_from_counts,
+from .lib import (DNA_SYMBOLS, CountMatrix, MotifBatch, Pipeline, ScoringMatrix, StripedSequence, StripedSequenceSet, background_from_counts,
                   fasta_names)
 
 DEFAULT_BATCH_BASES = 100_000_000
@@ -204,6 +210,25 @@ def best_set(pli: Pipeline, seqset: StripedSequenceSet, batch: MotifBatch):
     return motif.astype(np.int64), res.position[motif, rec], res.score[motif, rec], bounds
 
 
+def sites_by_motif(motif: np.ndarray, pos: np.ndarray, bounds: np.ndarray, n_motifs: int):
+    """The hits of ``scan_set`` / ``best_set`` (ordered by record) as the sites ``windows`` and ``count_sites`` take: per motif
+    a pair of (record, position) arrays, and ``order`` / ``starts`` with motif i's sites at ``order[starts[i]:starts[i + 1]]``
+    of the hit arrays."""
+    rec = np.repeat(np.arange(len(bounds) - 1, dtype=np.int64), np.diff(bounds))
+    order = np.argsort(motif, kind="stable")
+    starts = np.concatenate(([0], np.cumsum(np.bincount(motif, minlength=n_motifs)))).astype(np.int64)
+    rec, pos = rec[order], pos[order]
+    return [(rec[a:b], pos[a:b]) for a, b in zip(starts[:-1], starts[1:])], order, starts
+
+
+def window_text(win: np.ndarray, reverse: bool) -> np.ndarray:
+    """A ``(count, width)`` array of DNA symbol indices as ``count`` strings; ``reverse``: reverse-complemented."""
+    if reverse:
+        win = np.array([2, 3, 0, 1, 4], dtype=np.uint8)[win[:, ::-1]]
+    letters = np.ascontiguousarray(np.frombuffer(DNA_SYMBOLS.encode("ascii"), dtype=np.uint8)[win])
+    return letters.view(f"S{win.shape[1]}").reshape(-1).astype(str)
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
@@ -231,6 +256,10 @@ def build_parser() -> argparse.ArgumentParser:
                          "or the composition of the input, counted on the device in a first pass over the file")
     ap.add_argument("--composition", metavar="PATH",
                     help="also write a TSV with one line per record: seq_index, seq_name, length and the count of every symbol")
+    ap.add_argument("--matched", action="store_true",
+                    help="append a column `matched`: the text of the hit's window, reverse-complemented for strand -")
+    ap.add_argument("--site-matrices", metavar="PATH",
+                    help="also write a JASPAR-2016 file with, per motif, the count matrix of all its hits' windows")
     return ap
 
 
@@ -306,7 +335,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     n_hits = 0
     with contextlib.ExitStack() as files:
         out = files.enter_context(open(args.output, "w"))
-        out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue\n")
+        out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue" + ("\tmatched" if args.matched else "") + "\n")
+        site_totals = [np.zeros((m, len(DNA_SYMBOLS)), dtype=np.int64) for m in lengths] if args.site_matrices else None
         composition = files.enter_context(open(args.composition, "w")) if args.composition else None
         if composition is not None:
             composition.write("seq_index\tseq_name\tlength\t" + "\t".join(DNA_SYMBOLS) + "\n")
@@ -320,21 +350,38 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                 table = seqset.count_symbols().tolist()
                 for r, (name, length) in enumerate(zip(names, seqset.lengths.tolist())):
                     composition.write(f"{first_index + r + 1}\t{name}\t{length}\t" + "\t".join(map(str, table[r])) + "\n")
+            # the windows of the hits, read out of the resident set: one call per strand, whatever the number of hits
+            matched = [None] * len(found)
+            if args.matched or site_totals is not None:
+                for si, (strand, (motif, pos, _, bounds)) in enumerate(found):
+                    sites, order, starts = sites_by_motif(motif, pos, bounds, len(records))
+                    if args.matched:
+                        matched[si] = np.empty(len(motif), dtype=object)
+                        for mi, (win, _) in enumerate(seqset.windows(sites, lengths)):
+                            matched[si][order[starts[mi]:starts[mi + 1]]] = window_text(win, strand == "-")
+                    if site_totals is not None:
+                        for total, mat in zip(site_totals, seqset.count_sites(sites, lengths)[0]):
+                            total += (mat.reverse_complement() if strand == "-" else mat).data     # pwm/mod.rs:313-321
             wrote = 0
             for r, name in enumerate(names):
-                for (strand, (motif, pos, score, bounds)), pvs in zip(found, pvalues):
+                for (strand, (motif, pos, score, bounds)), pvs, texts in zip(found, pvalues, matched):
                     a, b = int(bounds[r]), int(bounds[r + 1])
                     pv = [None] * (b - a) if pvs is None else pvs[a:b].tolist()
-                    for mi, p, s, q in zip(motif[a:b].tolist(), pos[a:b].tolist(), score[a:b].tolist(), pv):
+                    tail = [""] * (b - a) if texts is None else ["\t" + t for t in texts[a:b].tolist()]
+                    for mi, p, s, q, t in zip(motif[a:b].tolist(), pos[a:b].tolist(), score[a:b].tolist(), pv, tail):
                         if q is None:
                             q = direct[mi].score_distribution.pvalue(s)   # main.rs:335: motif.dist
                         out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{p}\t{strand}\t{_fmt_score(s)}\t"
-                                  f"{_fmt_exp(q)}\n")
+                                  f"{_fmt_exp(q)}{t}\n")
                     wrote += b - a
             return wrote
 
         for first, names, seqset in sets():
             n_hits += write_set(first, names, seqset)
+        if site_totals is not None:
+            if any(int(t.max(initial=0)) > 0xFFFFFFFF for t in site_totals):
+                raise OverflowError("--site-matrices: a site count exceeds the u32 of a count matrix")
+            lmio.write([lmio.Record(r.id, r.description, CountMatrix(t)) for r, t in zip(records, site_totals)], args.site_matrices)
     print(f"Wrote {n_hits} hits to {args.output}")
     return 0
 
