@@ -189,6 +189,11 @@ int lm_hip_ctx_set_xcd_remap(lm_hip_ctx *ctx, int enabled);
  * 2 fused threshold); the store kernel's tracking forms (lm_hip_ctx_set_track_argmax:
  * template modes 3 and 5 in a rocprofv3 trace) report as "score_c32<M,0>". */
 const char *lm_hip_ctx_last_kernel(lm_hip_ctx *ctx);
+/* Diagnostic: rows per stream (T) of the last plain store launch on this context (score_into without the tracked
+ * maximum) when ONE C = 32 store kernel carried it; 0 when it took another route, motifs stored in slices (more than
+ * 36 rows) included.  Lengths whose kernel stores score
+ * rows in pairs always report an even number (lm_hip_ctx_set_rows_per_stream rounds to the nearest such length). */
+unsigned long long lm_hip_ctx_last_stream_rows(lm_hip_ctx *ctx);
 /* Diagnostic: what the last fused threshold scan on this context (single or batched) produced -- hits, and CANDIDATES: the
  * pieces of up to 32 rows the discrete prefilter flagged for exact re-scoring.  Candidates per hit is how much a
  * sequence costs beyond the scan itself (low-complexity tracts and N runs raise it: profiles/r05_realistic_inputs.json).

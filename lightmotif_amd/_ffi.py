@@ -84,6 +84,7 @@ SIGNATURES = {
     "lm_hip_ctx_set_option": (C.c_int, [_vp, C.c_char_p, C.c_double]),
     "lm_hip_ctx_set_xcd_remap": (C.c_int, [_vp, C.c_int]),
     "lm_hip_ctx_last_kernel": (C.c_char_p, [_vp]),
+    "lm_hip_ctx_last_stream_rows": (C.c_ulonglong, [_vp]),
     "lm_hip_ctx_last_scan_counts": (C.c_int, [_vp, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]),
     "lm_hip_ctx_last_scan_kernel_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "lm_hip_ctx_last_phases_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),

@@ -576,6 +576,8 @@ int lm_hip_ctx_set_xcd_remap(lm_hip_ctx *ctx, int enabled)  // round-4 ABI, a no
 
 const char *lm_hip_ctx_last_kernel(lm_hip_ctx *ctx) { return ctx ? ctx->last_kernel : ""; }
 
+unsigned long long lm_hip_ctx_last_stream_rows(lm_hip_ctx *ctx) { return ctx ? ctx->last_stream_rows : 0; }
+
 int lm_hip_ctx_last_scan_counts(lm_hip_ctx *ctx, unsigned long long *hits, unsigned long long *candidates)
 {
     if (!ctx)

@@ -214,6 +214,7 @@ struct lm_hip_ctx {
     unsigned long long last_hit_count = 0;  // sizes the next fused-threshold hit list
     unsigned long long last_cand_count = 0; // ... and its candidate list
     const char *last_kernel = "";
+    unsigned long long last_stream_rows = 0;  // rows per stream T of the last plain store launch of one C = 32 kernel (0: another route)
     // lm_hip_score_u8*: device tables of the DiscreteMatrix used last (a scanner scores the same
     // matrix block after block); `u8_key` = {m, k, pairs} + the weights they were built from
     lm::Scratch u8_tables;

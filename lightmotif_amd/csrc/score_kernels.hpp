@@ -263,6 +263,28 @@ __device__ __forceinline__ void record_hit(const FusedOut &fo, unsigned long lon
     }
 }
 
+// Paired row stores: the plain DNA store kernel with dword symbol loads, C = 32, M = 16 and 20 (every DNA motif of 13 ... 20
+// rows on a 4-byte aligned matrix), the kernels that were measured against their single-row form and won or were level
+// (profiles/r07_store_pairs_ab.json, r07_store_pairs_msweep.json).  M = 24 was built and measured too: 1.054-1.057 ms per
+// Gbp against 1.014-1.034 with single rows -- from there on the LDS gather binds, not the write pattern.  The byte-load
+// forms and the protein (WIDE) kernels were not measured and keep single rows.  A half-wave store of one score row covers 128
+// bytes; the write pattern, not the arithmetic, bounds that kernel.  Here the two half-waves of a
+// wavefront keep their own streams but exchange completed rows with one v_permlane32_swap per two outputs, after which
+// one register holds [stream A: row i | row i + 1] across the lane halves and the other [stream B: row i | row i + 1]:
+// every store instruction writes 256 contiguous bytes, addressed as a wave-uniform base per stream plus the lane number.
+// Output i of a stream pairs with i + 1 for even i, so streams are even: T = q*M + 1 + R with R = store_extra_rows(M)
+// further full steps between the FIRST group and the first MAIN group (R is odd for even M); the later groups run with
+// their slot phase shifted by R, which keeps every register index a constant of the unrolled step.  R is chosen so
+// that three-group streams are 64 rows = 8 KB of score rows, and stream starts 256-byte aligned.
+// (M = 4, 8, 12 could not simply follow: with every block of a group requested ahead, a shifted stream's last, partly used
+//  4-row symbol block would be requested by the group before the LAST one, past the rows the stream may read)
+// `ql`: dword symbol loads (QL of score_c32), `wide`: the kernels of alphabets beyond 16 symbols
+constexpr bool store_pairs(int m, int mode, int oc, int ql, int wide)
+{
+    return mode == 0 /* MODE_STORE */ && oc == 32 && ql != 0 && wide == 0 && (m == 16 || m == 20);
+}
+constexpr int store_extra_rows(int m) { return 63 % m; }
+
 // Tuning constants of score_c32 (every alternative was measured and its losing side removed; HISTORY 4.7-4.8 and the
 // profiles/r0*_*_ab.txt files keep the numbers):
 //   kScorePF  global prefetch distance in steps of the byte-load form: the symbol byte of step k + PF is requested
@@ -286,6 +308,9 @@ constexpr int score_min_waves_base(int m) { return m <= 20 ? 6 : m <= 40 ? 4 : 3
 //  1.11 -> 0.99 ms, M = 33 1.48 -> 1.04 per Gbp, the other modes and lengths unchanged; tools/fused_ab.sh, round 3)
 // (the tracked store of M <= 20 takes 74 VGPRs = six wavefronts where the plain store's 68 allow seven; compiled against a
 //  bound of seven it fits 72 + 2 spills and runs 2 % SLOWER at M = 20, equal at 12 / 16: profiles/r03_track_ab.txt)
+// (the paired plain store of M = 16, 20 takes 74 - 76 VGPRs = six wavefronts where the single-row one took 67 - 68 = seven.
+//  Against a bound of seven it fits 72 with two spills inside the MAIN group and runs 1.00 ms per Gbp at M = 20 where the
+//  six-wavefront build runs 0.918 and the single-row kernel 0.958: profiles/r07_store_pairs_ab.json, lib "w7")
 constexpr int score_min_waves(int m, int mode)
 {
     return m <= 40 ? ((mode == 2 /* MODE_THRESHOLD */ && m > 28 && m <= 36) ? 3
@@ -478,44 +503,58 @@ enum : int { PHASE_FIRST = 0, PHASE_MAIN = 1, PHASE_LAST = 2 };
 // the output row completed by step t is o0 + t - (M-1)); `orow` = output row completed by
 // the group's first step (in the FIRST group only step M-1 completes a row).
 // `sym` is a ring of symbol bytes indexed by step mod M (only ~PF are live).
-template <int M, int MODE, int PF, int PHASE, int QL = 0, int OC = 32, int WIDE = 0>
+// SH: the group starts SH steps into its frame of M steps (`sp`, `op`, `pa` / `pb` point at the frame's step 0): ring
+// positions and rows are counted from there (kk = k + SH).  NSTEPS: steps taken (the R extra steps are a short MAIN group).
+// PAIR: paired row stores through the wave-uniform `pa` / `pb` (stream of the lower / upper half-wave) instead of `op`.
+template <int M, int MODE, int PF, int PHASE, int QL = 0, int OC = 32, int WIDE = 0, int SH = 0, int NSTEPS = M, int PAIR = 0>
 __device__ __forceinline__ void score_group(float (&acc)[M], unsigned (&sym)[M],
                                             const uint8_t *__restrict__ sp,
                                             const char *__restrict__ tab,
                                             float *__restrict__ op, const unsigned tbase,
                                             const int col, float &best_v, unsigned &best_t,
                                             const FusedOut &fo, const unsigned shq, float &init_next,
-                                            float (&initq)[kContinueAhead], const bool prelast)
+                                            float (&initq)[kContinueAhead], const bool prelast,
+                                            unsigned *pa = nullptr, unsigned *pb = nullptr)
 {
     constexpr int NW = 4 * ((M + 3) / 4);
     constexpr int NB = M / 4;                  // QL: 4-row symbol blocks per group (M % 4 == 0)
     constexpr int PFB = NB > 3 ? 3 : NB;       // QL: blocks requested ahead of use
+    static_assert(SH == 0 || (PHASE != PHASE_FIRST && MODE == MODE_STORE), "shifted groups: the paired store kernel");
+    static_assert(!PAIR || M % 2 == 0, "which step completes the second row of a pair must be a constant");
 #pragma unroll
-    for (int k = 0; k < M; ++k) {
+    for (int k = 0; k < NSTEPS; ++k) {
+        const int kk = k + SH;  // step within the frame (constant after unrolling)
         // (1) request the symbol byte PF steps ahead (stays inside the stream's
         //     T+M-1 input rows: the LAST group does not look past its end)
         unsigned s_now = 0;
         if (QL) {
             // sym[] holds dword blocks (see quad_symbol); `sp` = this lane's row of block 0
-            const unsigned d = sym[k / 4];
-            s_now = (k % 4 == 0)   ? quad_symbol<0>(d, shq)
-                    : (k % 4 == 1) ? quad_symbol<1>(d, shq)
-                    : (k % 4 == 2) ? quad_symbol<2>(d, shq)
-                                   : quad_symbol<3>(d, shq);
-            if (k % 4 == 3 && (PHASE != PHASE_LAST || k / 4 + PFB < NB))
-                sym[(k / 4 + PFB) % NB] = *reinterpret_cast<const unsigned *>(sp + (k / 4 + PFB) * 128);
+            const unsigned d = sym[(kk / 4) % NB];
+            s_now = (kk % 4 == 0)   ? quad_symbol<0>(d, shq)
+                    : (kk % 4 == 1) ? quad_symbol<1>(d, shq)
+                    : (kk % 4 == 2) ? quad_symbol<2>(d, shq)
+                                    : quad_symbol<3>(d, shq);
+            constexpr int LASTKK = M - 1 + SH;  // the LAST group's final step: nothing beyond its row is the stream's
+            if (kk % 4 == 3 && (PHASE != PHASE_LAST || kk / 4 + PFB <= LASTKK / 4)) {
+                const uint8_t *bp = sp + (kk / 4 + PFB) * 128;
+                // a shifted LAST group ends inside a block: the lanes of the rows behind it read the block before
+                // (any row of the matrix will do, their symbols are never used)
+                if (PHASE == PHASE_LAST && LASTKK % 4 != 3 && kk / 4 + PFB == LASTKK / 4)
+                    bp -= (shq > 8u * (LASTKK % 4)) ? 128 : 0;
+                sym[(kk / 4 + PFB) % NB] = *reinterpret_cast<const unsigned *>(bp);
+            }
         } else if (PF > 0) {
             if (PHASE != PHASE_LAST || k + PF < M)
-                sym[(k + PF) % M] = sp[(k + PF) * 32];
+                sym[(kk + PF) % M] = sp[(kk + PF) * 32];
         } else {
-            sym[k] = sp[k * 32];
+            sym[kk % M] = sp[kk * 32];
         }
         // (2) the PSSM column of this step's symbol
         float w[NW];
         if (edge_reads_whole(M) && PHASE != PHASE_MAIN) {
             // FIRST: outputs started at steps 0..k -> weights 0..k.  LAST: the stream's last output
             // starts at the group's step 0, so step k still needs weights k..M-1
-            const unsigned sy = QL ? s_now : sym[k];
+            const unsigned sy = QL ? s_now : sym[kk % M];
 #pragma unroll
             for (int i = 0; i < NW; ++i)
                 w[i] = 0.0f;
@@ -526,7 +565,7 @@ __device__ __forceinline__ void score_group(float (&acc)[M], unsigned (&sym)[M],
         } else if (QL) {
             lds_fetch_column<M, WIDE>(w, tab, s_now);
         } else {
-            lds_fetch_column<M, WIDE>(w, tab, sym[k]);
+            lds_fetch_column<M, WIDE>(w, tab, sym[kk % M]);
         }
         // MODE_CONTINUE: the output started at this step resumes from the partial sum in its cell
         // (requested one step ago); request the next step's.  The row started at step k is stored
@@ -549,22 +588,40 @@ __device__ __forceinline__ void score_group(float (&acc)[M], unsigned (&sym)[M],
                 initq[k % CD] = *src;
             }
         }
-        // (3) P[j][s] goes to the output row started j steps ago: slot (k - j) mod M.
+        // (3) P[j][s] goes to the output row started j steps ago: slot (kk - j) mod M.
+        // PAIR: frames start at even steps of the stream (M is even) and step M - 1 completes output 0, so a step with
+        // even kk completes an ODD output.  Its partner, completed one step earlier, still sits in the slot this step
+        // starts anew (kk mod M): the new start waits until the pair is on its way.
+        const bool second = PAIR && PHASE != PHASE_FIRST && kk % 2 == 0;
 #pragma unroll
         for (int j = 0; j < M; ++j) {
-            const int slot = (k - j + M) % M;
-            if (j == 0)
-                acc[slot] = init + w[0];  // T::default() + P[0][s]   (pli/mod.rs:98,101), or the partial sum
-            else
+            const int slot = (kk - j + M) % M;
+            if (j == 0) {
+                if (!second)
+                    acc[slot] = init + w[0];  // T::default() + P[0][s]   (pli/mod.rs:98,101), or the partial sum
+            } else {
                 acc[slot] = acc[slot] + w[j];
+            }
         }
-        // (4) the slot started at step k-(M-1) is complete.
+        // (4) the slot started at step kk-(M-1) is complete.
         if (PHASE != PHASE_FIRST || k == M - 1) {
-            const float score = acc[(k + 1) % M];
+            const float score = acc[(kk + 1) % M];
             if (mode_tracks_cell(MODE) && PHASE == PHASE_FIRST)
                 init_next = score;  // (MODE_CONTINUE's carrier is free in these modes) the stream's first output
-            if (mode_stores(MODE))
-                __builtin_nontemporal_store(score, op + k * OC);  // streaming: the matrix is never read back by this kernel
+            if (PAIR) {
+                if (second) {
+                    // lanes 32-63 of the first operand change places with lanes 0-31 of the second: r[0] = the lower
+                    // half-wave's rows (kk - 1 | kk), r[1] = the upper half-wave's.  (Stored as the words the builtin
+                    // returns: with both results cast back to float this hipcc stores the first one twice.)
+                    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, acc[kk % M]),
+                                                                    __builtin_bit_cast(unsigned, score), false, false);
+                    const unsigned lane = threadIdx.x & 63u;
+                    __builtin_nontemporal_store(r[0], pa + (kk - 1) * 32 + lane);
+                    __builtin_nontemporal_store(r[1], pb + (kk - 1) * 32 + lane);
+                    acc[kk % M] = init + w[0];  // the start that waited
+                }
+            } else if (mode_stores(MODE))
+                __builtin_nontemporal_store(score, op + kk * OC);  // streaming: the matrix is never read back by this kernel
             if (MODE == MODE_STORE_ARGMAX) {
                 // value only (one v_max_f32; NaN operands are ignored, the NaN start value
                 // survives only if every score was NaN): the cell is located afterwards in
@@ -573,7 +630,7 @@ __device__ __forceinline__ void score_group(float (&acc)[M], unsigned (&sym)[M],
             } else if (mode_tracks_cell(MODE)) {
                 if (score >= best_v) {  // same `>=` as pli/mod.rs:146, NaN never passes
                     best_v = score;
-                    best_t = tbase + k;  // scalar + constant: no per-lane arithmetic
+                    best_t = tbase + kk;  // scalar + constant: no per-lane arithmetic
                 }
             } else if (MODE == MODE_THRESHOLD) {
                 // Hits are rare (a p = 1e-5 tail).  The hot loop only tracks the
@@ -671,7 +728,8 @@ __device__ __forceinline__ void emit_candidates(const unsigned long long hit_gro
 
 // C = 32, seq stride 32 B, out stride 32 floats.  Grid: ceil(nstreams / 8) blocks.
 // Every stream sweeps exactly T = q*M + 1 output rows, q >= 1, i.e. T + M - 1 =
-// (q+1)*M steps = one FIRST group, q-1 MAIN groups and one LAST group.  The last
+// (q+1)*M steps = one FIRST group, q-1 MAIN groups and one LAST group (the paired store kernels: T = q*M + 1 + R,
+// R full steps behind the FIRST group, see store_pairs).  The last
 // stream is shifted back so that it ends at row_end; idle half-waves re-do the
 // last stream (identical values -> benign duplicates).
 template <int M, int MODE, int QLREQ = 0, int OC = 32, int WIDE = 0>
@@ -709,6 +767,8 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
     static_assert(OC == 32 || (OC == 16 && MODE == MODE_STORE), "C = 16 is built for the plain store kernel");
     // quad-gathered symbol loads need whole 4-row blocks per group
     constexpr int QL = (QLREQ && M % 4 == 0) ? 1 : 0;
+    constexpr int PAIR = store_pairs(M, MODE, OC, QL, WIDE) ? 1 : 0;
+    constexpr int R = PAIR ? store_extra_rows(M) : 0;
     const int lane = threadIdx.x & 63;
     const int col = lane & (OC - 1);
     // (plain dispatch order = one compact window of rows in flight; an XCD-aware remap -- each XCD one contiguous
@@ -732,7 +792,25 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
     const uint8_t *sp = QL ? seq + (in0 + (col & 3)) * 32 + (col >> 2) * 4 : seq + in0 * 32 + col;
     // output row completed by step t is o0 + t - (M-1); `op` tracks step 0 of the group
     const long long orow = (long long)(o0 - row_begin) - (M - 1);
-    float *op = mode_stores(MODE) ? out + orow * OC + col : nullptr;
+    float *op = (mode_stores(MODE) && !PAIR) ? out + orow * OC + col : nullptr;
+    // PAIR: the score rows of the wavefront's two streams as wave-uniform pointers (frame step 0, like `op`); a store
+    // adds the lane number and a constant, and the pointers advance with the frames, so no offset outgrows 32 bits.
+    // (The symbol loads keep their per-lane pointer: given a uniform base and a lane offset the compiler folds the two
+    //  back into one 64-bit address per lane.)
+    unsigned *pa = nullptr, *pb = nullptr;
+    if (PAIR) {
+        const unsigned long long s0 =
+            (bid * (BLK / 64) + (unsigned)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 2;
+        auto first_row = [&](unsigned long long s) {  // the same rules as `stream` / `o0` above
+            if (s >= nstreams)
+                s = nstreams - 1;
+            const unsigned long long o = row_begin + s * T;
+            return o + T > row_end ? row_end - T : o;
+        };
+        const unsigned long long oa = first_row(s0), ob = first_row(s0 + 1);
+        pa = reinterpret_cast<unsigned *>(out) + ((long long)(oa - row_begin) - (M - 1)) * 32;
+        pb = reinterpret_cast<unsigned *>(out) + ((long long)(ob - row_begin) - (M - 1)) * 32;
+    }
 
     constexpr int PFE = PF < M ? PF : M - 1;  // look-ahead stays inside one group
     float acc[M];
@@ -766,7 +844,7 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
     for (int d = 0; d < kContinueAhead; ++d)  // rows started at steps 0 .. CD-1 of the stream (T >= M + 1 rows: they exist)
         initq[d] = (MODE == MODE_CONTINUE && d < continue_ahead(M)) ? op[(d + M - 1) * OC] : 0.0f;
 
-    const unsigned long long ngroups = (T + M - 1) / M;  // exact: T = q*M + 1, >= 2
+    const unsigned long long ngroups = (T - R + M - 1) / M;  // exact: T = q*M + 1 + R, >= 2
 
     // Fused threshold: the hot loop must stay branch-free (any `if` inside the
     // unrolled groups wrecks the schedule: 230 VGPRs / spills), so a lane only
@@ -788,25 +866,36 @@ __global__ __attribute__((amdgpu_flat_work_group_size(1, kBlock),
         }
     };
 
-    score_group<M, MODE, PFE, PHASE_FIRST, QL, OC, WIDE>(acc, sym, sp, lds_raw, op, tbase, col, best_v,
-                                                best_t, fo, shq, init_next, initq, ngroups == 2);
+    score_group<M, MODE, PFE, PHASE_FIRST, QL, OC, WIDE, 0, M, PAIR>(acc, sym, sp, lds_raw, op, tbase, col, best_v,
+                                                best_t, fo, shq, init_next, initq, ngroups == 2, pa, pb);
     const float first_out = init_next;  // MODE_STORE_TRACK: the stream's first output (scores[0][0] for stream 0, column 0)
     note_group();
-    for (unsigned long long g = 1; g + 1 < ngroups; ++g) {
+    auto next_frame = [&]() {
         sp += M * 32;
         tbase += M;
-        if (mode_stores(MODE))
+        if (mode_stores(MODE) && !PAIR)
             op += M * OC;
-        score_group<M, MODE, PFE, PHASE_MAIN, QL, OC, WIDE>(acc, sym, sp, lds_raw, op, tbase, col,
-                                                   best_v, best_t, fo, shq, init_next, initq, g + 2 == ngroups);
+        if (PAIR) {
+            pa += M * 32;
+            pb += M * 32;
+        }
+    };
+    if constexpr (R > 0) {  // the R extra steps open the frame the first MAIN (or the LAST) group goes on in
+        next_frame();
+        score_group<M, MODE, PFE, PHASE_MAIN, QL, OC, WIDE, 0, R, PAIR>(acc, sym, sp, lds_raw, op, tbase, col, best_v,
+                                                    best_t, fo, shq, init_next, initq, false, pa, pb);
+    }
+    for (unsigned long long g = 1; g + 1 < ngroups; ++g) {
+        if (R == 0 || g > 1)
+            next_frame();
+        score_group<M, MODE, PFE, PHASE_MAIN, QL, OC, WIDE, R, M, PAIR>(acc, sym, sp, lds_raw, op, tbase, col,
+                                                   best_v, best_t, fo, shq, init_next, initq, g + 2 == ngroups, pa, pb);
         note_group();
     }
-    sp += M * 32;
-    tbase += M;
-    if (mode_stores(MODE))
-        op += M * OC;
-    score_group<M, MODE, PFE, PHASE_LAST, QL, OC, WIDE>(acc, sym, sp, lds_raw, op, tbase, col, best_v,
-                                               best_t, fo, shq, init_next, initq, false);
+    if (R == 0 || ngroups > 2)
+        next_frame();
+    score_group<M, MODE, PFE, PHASE_LAST, QL, OC, WIDE, R, M, PAIR>(acc, sym, sp, lds_raw, op, tbase, col, best_v,
+                                               best_t, fo, shq, init_next, initq, false, pa, pb);
     note_group();
     if (MODE == MODE_THRESHOLD && gleft != G) {  // the last, partly filled note
         ++nnotes;

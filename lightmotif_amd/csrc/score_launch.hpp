@@ -31,6 +31,8 @@ struct C32Plan {
 // separately hipMalloc'ed buffers and lost 3 % inside one large arena or under PyTorch's
 // allocator: eight distant windows instead of one compact one.  Removed in round 5; numbers in
 // profiles/r01_kbench5_ab.txt, r01_kbench6_place.txt.)
+// `plain_store`: the plan is for the plain store kernel with dword symbol loads (SLOT_STORE_QL), whose streams are
+// T = q*M + 1 + R rows where it stores rows in pairs (score_kernels.hpp: store_pairs, store_extra_rows)
 // `prefilter`: 0 = exact kernels, 1 = one-symbol prefilter (streams of q*MP + 1 rows),
 // 2 = pair-symbol prefilter (streams of q*RING + 2 rows)
 // what the planner needs to know about the matrix (a.pssm may be absent: u8 scores)
@@ -40,7 +42,7 @@ struct MotifShape {
 };
 
 C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a, bool store, int prefilter = 0,
-                 size_t batch = 1, unsigned long long default_rows = 0, bool allow16 = false);
+                 size_t batch = 1, unsigned long long default_rows = 0, bool allow16 = false, bool plain_store = false);
 
 // How the exact C = 32 kernels see a motif: up to kMaxFastM rows as they are (byte symbol loads, any length);
 // kMaxFastM < M <= kMaxLongM as ONE slice padded with leading zero rows to a multiple of 4 (the long family:

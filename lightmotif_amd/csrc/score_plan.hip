@@ -190,7 +190,7 @@ C32Plan plan_c32(const lm_hip_ctx *ctx, const ScoreArgs &a, bool store, int pref
 // `allow16`: the caller also has a kernel for C = 16 (plain store, score rows of 16 floats; a
 // wavefront then carries four streams)
 C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a, bool store,
-                        int prefilter, size_t batch, unsigned long long default_rows, bool allow16)
+                        int prefilter, size_t batch, unsigned long long default_rows, bool allow16, bool plain_store)
 {
     C32Plan p;
     const size_t K = ms.k;
@@ -198,9 +198,11 @@ C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a
     const size_t M = prefilter == 2   ? (size_t)prefilter2_ring((int)ms.m)
                      : prefilter == 1 ? (size_t)prefilter_mp((int)ms.m, lds_wide((int)K))
                                       : ms.m;
-    const size_t extra = prefilter == 2 ? 2 : 1;  // rows of a stream beyond q groups
     const unsigned long long n = a.row_end - a.row_begin;
     const bool c16 = allow16 && store && prefilter == 0 && a.cols == 16;
+    // the kernel stores rows in pairs: R full steps more per stream, which makes every stream length even
+    const bool pairs = plain_store && store && prefilter == 0 && !c16 && store_pairs((int)ms.m, MODE_STORE, 32, 1, lds_wide((int)K) ? 1 : 0);
+    const size_t extra = (prefilter == 2 ? 2 : 1) + (pairs ? (size_t)store_extra_rows((int)ms.m) : 0);  // rows of a stream beyond q groups
     if ((a.cols != 32 && !c16) || a.seq_stride != 32 || (store && a.out_stride != a.cols))
         return p;
     if (ms.m < 1 || ms.m > (size_t)(prefilter == 0 ? (store ? kMaxStoreM : kMaxLongM) : (prefilter == 2 && K == 5) ? kMaxPairM : kMaxFastM) || n < M + extra)
@@ -224,11 +226,15 @@ C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a
     // longer motifs are bound by the LDS gather and want the fill / drain groups amortised over
     // six groups (M = 28: T = 57 1.29 ms, T = 169 1.08; M = 33: T = 67 1.30, T = 199 1.22;
     // profiles/r02_edge_ab.txt).  Very short motifs keep ~24 rows per stream.
+    // Paired stores (even M, plain store): T = q*M + 1 + R with R = 63 % M, so up to M = 26 the default stream is
+    // q = 63 / M groups = 64 rows = 8 KB of score rows, every stream starts 256-byte aligned and no pair of rows
+    // straddles two streams; a requested length goes to the nearest q.
     unsigned long long target = ctx->rows_per_stream ? ctx->rows_per_stream
                                 : default_rows         ? default_rows
                                 : !store               ? 1024
                                 : prefilter != 0       ? 64
                                 : ms.m > 26            ? 6 * M
+                                : pairs                ? 64
                                                        : std::max<size_t>(3 * M, 24);
     // keep at least ~4 streams per SIMD lane-half in flight on small inputs
     // Enough workgroups for several rounds of the chip's resident capacity (6 x 256 CUs
@@ -240,7 +246,7 @@ C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a
     if (n / target < want_streams)
         target = std::max<unsigned long long>(n / want_streams, 1);
     target = std::min<unsigned long long>(target, 1ull << 30);  // step indices are 32-bit
-    unsigned long long q = std::max<unsigned long long>((target + M / 2) / M, 1);
+    unsigned long long q = std::max<unsigned long long>(((pairs ? target - std::min<unsigned long long>(target, extra) : target) + M / 2) / M, 1);
     if (q * M + extra > n)
         q = (n - extra) / M;
     if (q < 1)

@@ -52,6 +52,7 @@ unsigned tiled_records(const lm_hip_ctx *ctx, const ScoreArgs &a)
 int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
 {
     FusedOut fo{};
+    ctx->last_stream_rows = 0;
     const bool wide = lds_wide((int)a.pssm->k);
     const bool dwords = ctx->quad_loads && reinterpret_cast<uintptr_t>(a.d_seq) % 4 == 0;
     if (dwords && a.pssm->d_table_pad) {
@@ -59,10 +60,11 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
         // sums (0.0 + 0.0 + P[0] ... ), with the dword symbol loads and 4-row blocks of the M' kernel
         const size_t mp = a.pssm->m + a.pssm->lead;
         const MotifShape ms{mp, a.pssm->k, false};
-        const C32Plan pp = plan_c32(ctx, ms, a, true, 0, 1, store_rows_hint(mp, a.cols), true);
+        const C32Plan pp = plan_c32(ctx, ms, a, true, 0, 1, store_rows_hint(mp, a.cols), true, a.cols == 32);  // (32 columns: SLOT_STORE_QL)
         ScoreC32Launcher pfn = a.cols == 16 ? score_c32_lookup((int)mp, SLOT_STORE_C16, wide) : score_c32_lookup((int)mp, SLOT_STORE_QL, wide);
         if (pp.ok && pfn) {
             fo.lead_rows = (unsigned)a.pssm->lead;
+            ctx->last_stream_rows = pp.T;
             ctx->last_kernel = score_c32_name((int)mp, MODE_STORE);
             tally_launch(ctx, LM_HIP_FAMILY_C32, wide, mp, a.cols == 16 ? SLOT_STORE_C16 : SLOT_STORE_QL);
             LM_HIP_TRY(pfn(pp.grid, pp.lds, ctx->stream, a.d_seq, a.pssm->d_table_pad,
@@ -72,16 +74,18 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
         }
     }
     const bool c16 = a.cols == 16 && dwords && score_c32_lookup((int)a.pssm->m, SLOT_STORE_C16, wide);
+    const bool ql = dwords && !c16 && score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide);  // dword symbol loads (M % 4 == 0)
     const C32Plan p = a.pssm->m <= (size_t)kMaxFastM ? plan_c32(ctx, MotifShape{a.pssm->m, a.pssm->k, false}, a, true, 0, 1,
-                                                                  store_rows_hint(a.pssm->m, a.cols), c16)
+                                                                  store_rows_hint(a.pssm->m, a.cols), c16, ql)
                                                       : C32Plan{};  // longer: the slices below
     if (p.ok) {
         int slot = SLOT_STORE;
-        if (dwords && score_c32_lookup((int)a.pssm->m, SLOT_STORE_QL, wide))
-            slot = SLOT_STORE_QL;  // dword symbol loads (M % 4 == 0)
+        if (ql)
+            slot = SLOT_STORE_QL;
         if (c16)
             slot = SLOT_STORE_C16;  // four streams of 16 columns per wavefront
         ScoreC32Launcher fn = score_c32_lookup((int)a.pssm->m, slot, wide);
+        ctx->last_stream_rows = p.T;
         ctx->last_kernel = score_c32_name((int)a.pssm->m, MODE_STORE);
         tally_launch(ctx, LM_HIP_FAMILY_C32, wide, a.pssm->m, slot);
         LM_HIP_TRY(fn(p.grid, p.lds, ctx->stream, a.d_seq, a.pssm->d_table, (int)a.pssm->k,
@@ -101,7 +105,9 @@ int launch_score_store(lm_hip_ctx *ctx, const ScoreArgs &a)
             const MotifShape ms{part.m, a.pssm->k, false};
             ScoreArgs sa = a;
             sa.d_seq = a.d_seq + part.off * a.seq_stride;  // slice row j reads sequence row r + off + j
-            const C32Plan p = plan_c32(ctx, ms, sa, true);
+            // (the first slice is a plain store pass, with dword symbol loads where its length has them)
+            const C32Plan p = plan_c32(ctx, ms, sa, true, 0, 1, 0, false,
+                                       i == 0 && score_c32_lookup((int)part.m, SLOT_STORE_QL, wide) != nullptr);
             if (!p.ok) {
                 ok = false;
                 break;

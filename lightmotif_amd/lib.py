@@ -151,6 +151,12 @@ class Pipeline:
     def last_kernel(self) -> str:
         return self._L.lm_hip_ctx_last_kernel(self._h).decode()
 
+    @property
+    def last_stream_rows(self) -> int:
+        """Rows per stream T of the last plain store launch (``score_into`` without the tracked maximum) when one C = 32
+        store kernel carried it; 0 when it took another route (lm_hip_ctx_last_stream_rows)."""
+        return int(self._L.lm_hip_ctx_last_stream_rows(self._h))
+
     @staticmethod
     def _registry_rows(call) -> Dict[Tuple[str, int, int, str], int]:
         n = C.c_size_t(0)

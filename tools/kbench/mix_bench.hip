@@ -1,9 +1,10 @@
 // mix_bench -- how fast can a trivial kernel move the score kernel's traffic mix (1 B read : 4 B written)?
-// Development tool.  ./mix_bench [bytes_in]
+// Development tool.  ./mix_bench [bytes_in] [pairs]     ("pairs": only the paired-store comparison at the end)
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #define CK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #x, hipGetErrorString(e_)); exit(2); } } while (0)
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -254,6 +255,54 @@ __global__ __launch_bounds__(256) void mix_rows_w(const uint8_t *in, float *out,
     }
 }
 
+// the two halves of a wavefront on their OWN streams (as mix_rows), completed rows regrouped in registers: after one
+// v_permlane32_swap per two rows one register holds [A row r | A row r+1] across the lane halves and the other
+// [B row r | B row r+1], so every store instruction covers 256 contiguous bytes (dword per lane) and the stores
+// alternate between the two streams.  Addresses are a wave-uniform base per stream plus the lane number.  The last
+// stream is shifted back to end at `rows` and idle half-waves redo it, as in the score kernel; an odd T leaves one
+// row per stream to a half-wave store.
+template <int PFD>
+__global__ __launch_bounds__(256) void mix_rows_sw(const uint8_t *in, float *out, unsigned long long rows,
+                                                   unsigned long long T)
+{
+    static_assert(PFD % 2 == 0, "pairs of rows");
+    const unsigned lane = threadIdx.x & 63, half = lane >> 5, col = lane & 31;
+    const unsigned long long nstreams = (rows + T - 1) / T;
+    const unsigned long long wave = (unsigned long long)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    if (2 * wave >= nstreams) return;   // the whole wavefront
+    auto first_row = [&](unsigned long long s) {
+        if (s >= nstreams) s = nstreams - 1;
+        const unsigned long long o = s * T;
+        return o + T > rows ? rows - T : o;   // rows >= T
+    };
+    const unsigned long long oa = first_row(2 * wave), ob = first_row(2 * wave + 1);
+    const uint8_t *ip = in + (half ? ob : oa) * 32 + col;
+    float *pa = out + oa * 32, *pb = out + ob * 32;   // wave-uniform
+    const unsigned nrows = (unsigned)T;
+    unsigned ring[PFD];
+#pragma unroll
+    for (int k = 0; k < PFD; ++k) ring[k] = ip[k * 32];
+    for (unsigned r = 0; r < nrows; r += PFD) {
+#pragma unroll
+        for (int k = 0; k < PFD; k += 2) {
+            const float x0 = (float)ring[k], x1 = (float)ring[k + 1];
+            ring[k] = ip[(k + PFD) * 32];
+            ring[k + 1] = ip[(k + 1 + PFD) * 32];
+            if (r + k + 1 < nrows) {
+                const auto v = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, x0),
+                                                                __builtin_bit_cast(unsigned, x1), false, false);
+                // (stored as the unsigned words the builtin returns: with both results cast back to float this hipcc
+                //  stores the first one twice)
+                __builtin_nontemporal_store(v[0], reinterpret_cast<unsigned *>(pa) + (r + k) * 32 + lane);
+                __builtin_nontemporal_store(v[1], reinterpret_cast<unsigned *>(pb) + (r + k) * 32 + lane);
+            } else if (r + k < nrows) {
+                __builtin_nontemporal_store(x0, (half ? pb : pa) + (r + k) * 32 + col);
+            }
+        }
+        ip += PFD * 32;
+    }
+}
+
 // same, but 8 completed rows of a stream are staged in LDS and written as 1 KB by the whole wavefront
 __global__ __launch_bounds__(256) void mix_rows_lds(const uint8_t *in, f32x4 *out, unsigned long long rows,
                                                     unsigned long long T)
@@ -285,6 +334,13 @@ __global__ __launch_bounds__(256) void mix_rows_lds(const uint8_t *in, f32x4 *ou
     }
 }
 
+__global__ __launch_bounds__(256) void fill_pattern(uint8_t *in, unsigned long long n)
+{
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n;
+         i += (unsigned long long)gridDim.x * 256)
+        in[i] = (uint8_t)((i >> 5) * 7 + (i & 31) * 3);   // differs from row to row and from column to column
+}
+
 __global__ __launch_bounds__(256) void fill(f32x4 *out, unsigned long long n16)
 {
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n16;
@@ -311,10 +367,12 @@ int main(int argc, char **argv)
 {
     const unsigned long long n = argc > 1 ? strtoull(argv[1], nullptr, 10) : 1000000000ull;
     uint8_t *in; float *out;
-    CK(hipMalloc(&in, n + 64));
+    const bool pairs_only = argc > 2 && !strcmp(argv[2], "pairs");
+    CK(hipMalloc(&in, n + 4096));   // the row kernels request up to 2 * PFD rows past a stream's end
     CK(hipMalloc(&out, n * 4 + 64));
     CK(hipMemset(in, 3, n));
     auto rep = [&](const char *name, float ms) { printf("%-28s %8.3f ms  %7.1f GB/s\n", name, ms, 5.0 * n / ms / 1e6); };
+    if (!pairs_only)
     for (int g : {8192, 32768, 131072}) {
         char nm[64];
         snprintf(nm, sizeof nm, "mix_dw g=%d", g);
@@ -331,7 +389,7 @@ int main(int argc, char **argv)
         float ms = timeit([&] { hipLaunchKernelGGL(fill, dim3(g), dim3(256), 0, 0, (f32x4 *)out, n / 4); }, 20);
         printf("%-28s %8.3f ms  %7.1f GB/s\n", nm, ms, 4.0 * n / ms / 1e6);
     }
-    {
+    if (!pairs_only) {
         const unsigned long long rows = n / 32;
         for (unsigned long long T : {56ull, 60ull, 61ull, 64ull, 72ull, 80ull, 96ull, 128ull, 61ull, 64ull}) {
             const unsigned long long nstreams = (rows + T - 1) / T;
@@ -350,7 +408,7 @@ int main(int argc, char **argv)
             rep(nm, timeit([&] { hipLaunchKernelGGL(mix_rows_lds, dim3((unsigned)(rows8 / T / 8)), dim3(256), 0, 0, in, (f32x4 *)out, rows8, T); }, 20));
         }
     }
-    {   // XCD <-> address affinity: 4 GB written in chunks of 4 KB ... 1 MB per workgroup under four chunk permutations
+    if (!pairs_only) {   // XCD <-> address affinity: 4 GB written in chunks of 4 KB ... 1 MB per workgroup under four chunk permutations
         for (unsigned long long chunk_bytes : {4096ull, 16384ull, 65536ull, 1048576ull}) {
             const unsigned long long chunk16 = chunk_bytes / 16, nchunks = (n * 4) / chunk_bytes / 256 * 256;
             for (int mode = 0; mode < 4; ++mode) {
@@ -361,7 +419,7 @@ int main(int argc, char **argv)
             }
         }
     }
-    {   // the row pattern under every store cache policy (two rounds, interleaved)
+    if (!pairs_only) {   // the row pattern under every store cache policy (two rounds, interleaved)
         const unsigned long long rows = n / 32, T = 61;
         const unsigned grid = (unsigned)(((rows + T - 1) / T + 7) / 8);
         const char *names[7] = {"(none)", "nt", "sc0", "sc1", "sc0 sc1", "sc0 sc1 nt", "sc1 nt"};
@@ -381,7 +439,7 @@ int main(int argc, char **argv)
             }
         }
     }
-    {   // the row pattern at reduced occupancy (unused dynamic LDS as ballast): fewer streams open at once
+    if (!pairs_only) {   // the row pattern at reduced occupancy (unused dynamic LDS as ballast): fewer streams open at once
         const unsigned long long rows = n / 32, T = 61;
         const unsigned grid = (unsigned)(((rows + T - 1) / T + 7) / 8);
         for (unsigned lds : {0u, 20u << 10, 40u << 10, 53u << 10, 80u << 10, 160u << 10}) {
@@ -389,6 +447,36 @@ int main(int argc, char **argv)
             char nm[64];
             snprintf(nm, sizeof nm, "mix_rows T=61 lds=%uK", lds >> 10);
             rep(nm, timeit([&] { hipLaunchKernelGGL(mix_rows<12>, dim3(grid), dim3(256), lds, 0, in, out, rows, T); }, 20));
+        }
+    }
+    {   // two streams per wavefront, rows exchanged between the halves, 256-byte stores (five interleaved rounds: the
+        // spread between the rounds of one arm is the yardstick for the difference between arms)
+        const unsigned long long rows = n / 32;
+        hipLaunchKernelGGL(fill_pattern, dim3(8192), dim3(256), 0, 0, in, n);
+        for (unsigned long long T : {61ull, 64ull}) {   // the regrouped rows land where mix_rows puts them
+            CK(hipMemset(out, 0xff, rows * 128));
+            hipLaunchKernelGGL(mix_rows_sw<12>, dim3((unsigned)(((rows + T - 1) / T + 7) / 8)), dim3(256), 0, 0, in, out, rows, T);
+            const unsigned long long nchk = rows * 32 < (1ull << 20) ? rows * 32 : (1ull << 20);
+            float *h = (float *)malloc(nchk * 4);
+            unsigned long long bad = 0;
+            for (unsigned long long start : {0ull, rows * 32 - nchk}) {
+                CK(hipMemcpy(h, out + start, nchk * 4, hipMemcpyDeviceToHost));
+                for (unsigned long long i = 0; i < nchk; ++i)
+                    bad += h[i] != (float)(uint8_t)(((start + i) >> 5) * 7 + ((start + i) & 31) * 3);
+            }
+            free(h);
+            printf("mix_rows_sw<12> T=%llu check: %llu wrong of %llu\n", T, bad, 2 * nchk);
+            if (bad) return 1;
+        }
+        for (int round = 0; round < 5; ++round) {
+            for (unsigned long long T : {61ull, 64ull}) {
+                const unsigned grid = (unsigned)(((rows + T - 1) / T + 7) / 8);
+                char nm[64];
+                snprintf(nm, sizeof nm, "mix_rows<12> T=%llu", T);
+                rep(nm, timeit([&] { hipLaunchKernelGGL(mix_rows<12>, dim3(grid), dim3(256), 0, 0, in, out, rows, T); }, 20));
+                snprintf(nm, sizeof nm, "mix_rows_sw<12> T=%llu", T);
+                rep(nm, timeit([&] { hipLaunchKernelGGL(mix_rows_sw<12>, dim3(grid), dim3(256), 0, 0, in, out, rows, T); }, 20));
+            }
         }
     }
     return 0;
