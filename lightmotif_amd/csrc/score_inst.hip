@@ -29,20 +29,20 @@ template <int M>
 struct RegisterRange {
     static void run(const KernelRegistry &r)
     {
-        r.pre[M] = &score_c32_prefilter_launch<M>;
-        r.u8[M] = &score_c32_u8_launch<M>;  // DiscreteMatrix scores (score_u8.hpp)
+        r.pre[M] = &launch_scan<score_c32_prefilter<M>>;
+        r.u8[M] = &launch_scan<score_c32_u8<M>>;  // DiscreteMatrix scores (score_u8.hpp)
         if constexpr (M >= 2) {
-            r.pre2[M] = &score_c32_prefilter2_launch<M>;
-            r.pre2_protein[M] = &score_c32_prefilter2_launch<M, 21>;
+            r.pre2[M] = &launch_scan<score_c32_prefilter2<M>>;
+            r.pre2_protein[M] = &launch_scan<score_c32_prefilter2<M, 21>>;
             r.u8_pairs[M] = &score_c32_u8_pairs_launch<M>;
             if constexpr (prefilter2_multi(M) > 1)
                 r.pre2_multi[M] = &score_c32_prefilter2_multi_launch<M>;
         }
         fill_c32_row<M, 0>(r.c32[M]);
         // wide alphabets (protein)
-        r.prew[M] = &score_c32_prefilter_launch<M, 1>;
-        r.preblk[M] = &score_c32_prefilter_blk_launch<M>;
-        r.u8w[M] = &score_c32_u8_launch<M, 1>;
+        r.prew[M] = &launch_scan<score_c32_prefilter<M, kScorePF, 1>>;
+        r.preblk[M] = &launch_scan<score_c32_prefilter_blk<M>>;
+        r.u8w[M] = &launch_scan<score_c32_u8<M, kScorePF, 1>>;
         fill_c32_row<M, 1>(r.c32w[M]);
         if constexpr (M < LM_M_HI)
             RegisterRange<M + 1>::run(r);

@@ -39,11 +39,10 @@
 #include <cstdint>
 
 #include "lm_internal.hpp"
+#include "scan_stream.hpp"  // kBlock, GroupNotes: shared with the discrete scans
 
 namespace lm {
 
-constexpr int kBlock = 256;                      // threads per workgroup (4 wavefronts)
-constexpr int kStreamsPerBlock = kBlock / 32;    // 2 per wavefront
 constexpr int kMaxFastM = 36;        // largest motif the whole kernel family (every length, prefilters, u8) is built for
 // 36 < M <= 64: the exact f32 kernels only, for the padded lengths M' = 40, 44 ... 64 (leading zero rows, see
 // lm_hip_pssm::Part::lead): one pass over the sequence like the reference's AVX2 loop takes for any length
@@ -421,33 +420,7 @@ __device__ __forceinline__ unsigned quad_symbol(unsigned block_dword, unsigned s
     return (x >> shift) & 0xffu;
 }
 
-// One bit per NOTE (= G groups of a stream), up to 64 per stream, collected without a compare AND without a 64-bit shift by
-// a register (score_prefilter.hpp, prefilter_lookahead: such a shift by the last allocated VGPR is what broke the protein scans): the field shifts right one bit per
-// note and takes the note's flag in at bit 63, so after n notes they sit in its top n bits, oldest lowest.
-struct GroupNotes {
-    unsigned lo = 0, hi = 0;
-    // `mx`: bit 15 of a half = that half reached the threshold (the pair scans' biased sums, score_prefilter2.hpp: kFlagBits)
-    __device__ __forceinline__ void note(unsigned &mx)
-    {
-        const unsigned either = mx | (mx << 16);  // bit 31: one of the two halves reached the threshold
-        push(either);
-        mx = 0;
-    }
-    __device__ __forceinline__ void push(const unsigned flag31)  // bit 31 of `flag31` = the note's flag
-    {
-        lo = __builtin_amdgcn_alignbit(hi, lo, 1);  // (hi:lo) >> 1
-        hi = (hi >> 1) | (flag31 & 0x80000000u);
-    }
-    __device__ __forceinline__ unsigned long long finish(unsigned n) const  // n = notes taken, 1 ... 64 (wave-uniform)
-    {
-        // (hi:lo) >> (64 - n) with 32-bit operations only
-        const unsigned sh = 64u - n;
-        const unsigned a = sh >= 32u ? hi : lo, b = sh >= 32u ? 0u : hi, r = sh & 31u;
-        const unsigned out_lo = r ? (a >> r) | (b << (32u - r)) : a;
-        const unsigned out_hi = r ? (b >> r) : b;
-        return ((unsigned long long)out_hi << 32) | out_lo;
-    }
-};
+// (GroupNotes, the per-stream record of flagged groups: scan_stream.hpp)
 
 // ---- the linear lane map of 4-row symbol blocks (round 6; score_prefilter_blk.hpp) -----------------------------------
 // Lane l of a half-wave reads dword l of a block's 128 bytes (row q = l >> 3, columns 4b .. 4b + 3, b = l & 7) and accumulates

@@ -33,10 +33,10 @@ void LM_CAT(register_score_c32_long_, LM_LONG_M)(const KernelRegistry &r)
     fill_long_row<M, 1>(r.c32w[M]);
     // the pair-symbol prefilter scan (score_prefilter2.hpp) of the four exact lengths that pad to M: the fused
     // threshold / argmax of 36 < M <= 64 flag candidates with it like the shorter motifs do (DNA)
-    r.pre2[M - 3] = &score_c32_prefilter2_launch<M - 3>;
-    r.pre2[M - 2] = &score_c32_prefilter2_launch<M - 2>;
-    r.pre2[M - 1] = &score_c32_prefilter2_launch<M - 1>;
-    r.pre2[M] = &score_c32_prefilter2_launch<M>;
+    r.pre2[M - 3] = &launch_scan<score_c32_prefilter2<M - 3>>;
+    r.pre2[M - 2] = &launch_scan<score_c32_prefilter2<M - 2>>;
+    r.pre2[M - 1] = &launch_scan<score_c32_prefilter2<M - 1>>;
+    r.pre2[M] = &launch_scan<score_c32_prefilter2<M>>;
 }
 
 }  // namespace lm

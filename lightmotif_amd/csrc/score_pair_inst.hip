@@ -15,7 +15,7 @@ template <int M>
 struct RegisterPairRange {
     static void run(const KernelRegistry &r)
     {
-        r.pre2[M] = &score_c32_prefilter2_launch<M>;
+        r.pre2[M] = &launch_scan<score_c32_prefilter2<M>>;
         if constexpr (M < LM_PAIR_HI)
             RegisterPairRange<M + 1>::run(r);
     }

@@ -194,15 +194,17 @@ C32Plan plan_c32(const lm_hip_ctx *ctx, const MotifShape &ms, const ScoreArgs &a
 {
     C32Plan p;
     const size_t K = ms.k;
-    // rows per unrolled group: the motif length, padded for the prefilter kernels
-    const size_t M = prefilter == 2   ? (size_t)prefilter2_ring((int)ms.m)
-                     : prefilter == 1 ? (size_t)prefilter_mp((int)ms.m, lds_wide((int)K))
-                                      : ms.m;
+    // rows per unrolled group and rows completed by a stream's first group: the discrete scans' from the StreamGeom
+    // their kernels count groups with (scan_stream.hpp); the exact kernels step by the motif length
+    const StreamGeom geom = prefilter == 2   ? pair_geom((int)ms.m)
+                            : prefilter == 1 ? one_symbol_geom((int)ms.m, lds_wide((int)K))
+                                             : StreamGeom{(int)ms.m, 1};
+    const size_t M = (size_t)geom.step;
     const unsigned long long n = a.row_end - a.row_begin;
     const bool c16 = allow16 && store && prefilter == 0 && a.cols == 16;
     // the kernel stores rows in pairs: R full steps more per stream, which makes every stream length even
     const bool pairs = plain_store && store && prefilter == 0 && !c16 && store_pairs((int)ms.m, MODE_STORE, 32, 1, lds_wide((int)K) ? 1 : 0);
-    const size_t extra = (prefilter == 2 ? 2 : 1) + (pairs ? (size_t)store_extra_rows((int)ms.m) : 0);  // rows of a stream beyond q groups
+    const size_t extra = (size_t)geom.first + (pairs ? (size_t)store_extra_rows((int)ms.m) : 0);  // rows of a stream beyond q groups
     if ((a.cols != 32 && !c16) || a.seq_stride != 32 || (store && a.out_stride != a.cols))
         return p;
     if (ms.m < 1 || ms.m > (size_t)(prefilter == 0 ? (store ? kMaxStoreM : kMaxLongM) : (prefilter == 2 && K == 5) ? kMaxPairM : kMaxFastM) || n < M + extra)

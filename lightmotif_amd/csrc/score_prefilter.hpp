@@ -41,9 +41,7 @@ namespace lm {
 // "reached the threshold" flag in the pair scans (score_prefilter2.hpp: kFlagBits).  15 bits of resolution over the
 // matrix's score range: the over-estimate is at most 2 M quanta of range / 32000.
 constexpr unsigned kPrefilterTop = 32000u;
-// padded motif length: even (two accumulators per register); a multiple of 4 for wide alphabets, whose scan fetches symbols
-// in 4-row blocks that must not straddle a group (score_prefilter_blk.hpp) -- every user of a wide image shares that geometry
-constexpr int prefilter_mp(int m, int wide = 0) { return wide ? (m + 3) / 4 * 4 : (m + 1) / 2 * 2; }
+// (prefilter_mp, the padded motif length: scan_stream.hpp)
 // Symbol look-ahead of the byte-load scans, in steps: at most the ring of MP symbol registers minus the one being consumed.
 // (Round 5 shortened it to MP - 2 because the protein kernels of M = 7, 8 lost a quarter of their candidates at MP - 1.  The ring
 // was innocent: at MP - 1 those kernels used v0..v55 of 56 allocated VGPRs and v55 held the amount of the 64-bit shift that moved
@@ -106,7 +104,7 @@ __device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b)
     return __builtin_bit_cast(unsigned, __builtin_elementwise_min(x, y));
 }
 
-// (GroupNotes, the per-stream record of flagged groups, lives in score_kernels.hpp)
+// (GroupNotes, the per-stream record of flagged groups: scan_stream.hpp)
 
 // `mx` collects (packed max) every register that holds a just-completed sum.  Its other half
 // is the partial sum of an output still in flight; weights are >= 0, so a partial sum that
@@ -214,9 +212,8 @@ __device__ __forceinline__ void prefilter_group(unsigned (&acc2)[prefilter_mp(M,
     }
 }
 
-// Same geometry as score_c32<M, MODE_THRESHOLD> with M replaced by MP: every stream
-// sweeps T = q*MP + 1 outputs in (q+1) groups of MP steps.  `image` = the LDS image
-// described above; `td` = discrete threshold.
+// Stream geometry: one_symbol_geom(M, WIDE) (scan_stream.hpp), i.e. that of score_c32<M, MODE_THRESHOLD> with M
+// replaced by MP.  `image` = the LDS image described above; `td` = discrete threshold.
 template <int M, int PF = kScorePF, int WIDE = 0>
 __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
     const uint8_t *__restrict__ seq, const unsigned *__restrict__ image, const int K,
@@ -225,7 +222,7 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
     const FusedOut fo_in)
 {
     FusedOut fo = fo_in;
-    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform)
+    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform; the same lines in score_c32_prefilter_blk, score_c32_prefilter2)
         const BatchParams bp = fo_in.batch[blockIdx.y];
         image = static_cast<const unsigned *>(bp.table);
         td = bp.td;
@@ -246,30 +243,24 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
     const char *tab_even = lds_raw;
     const char *tab_odd = tab_even + (size_t)K * prefilter_stride_dw(M, WIDE) * 4;
 
-    const int lane = threadIdx.x & 63;
-    const int col = lane & 31;
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    const bool idle = stream >= nstreams;  // re-does the last stream, reports nothing
-    if (idle)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)
-        o0 = row_end - T;
+    const int col = threadIdx.x & 31;
+    const StreamPlace pl = place_stream(row_begin, row_end, T, nstreams);
+    const unsigned long long o0 = pl.o0;
 
     // padded output o' = o - SHIFT covers input rows o' .. o'+MP-1; its first row carries
     // the all-zero weight row, so when o0 == 0 that (non-existent) row is never loaded
     const uint8_t *sp = seq + (long long)(o0 - SHIFT) * 32 + col;
     constexpr int PFE = prefilter_lookahead(PF, MP);
+    static_assert(PFE >= 1, "the prefilter kernel needs a look-ahead of at least one step");
     unsigned acc2[NP];
     unsigned sym[MP];
 #pragma unroll
     for (int i = 0; i < NP; ++i)
         acc2[i] = 0;
+    // (the symbol ring zeroed, then the look-ahead: the same lines in score_c32_u8)
 #pragma unroll
     for (int j = 0; j < MP; ++j)
         sym[j] = 0;
-    static_assert(PFE >= 1, "the prefilter kernel needs a look-ahead of at least one step");
 #pragma unroll
     for (int j = 0; j < PFE; ++j) {
         if (j < SHIFT) {
@@ -280,9 +271,14 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
         }
     }
 
-    // wave-uniform 32-bit bookkeeping (T <= 2^30, score_plan.hip)
-    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T + MP - 1u) / (unsigned)MP));  // exact: T = q*MP + 1, >= 2
-    const unsigned G = (ngroups + 63u) / 64u;  // groups per note (= per bit of hit_groups)
+    constexpr StreamGeom GEOM = one_symbol_geom(M, WIDE);
+    // Wave-uniform 32-bit bookkeeping (T <= 2^30, score_plan.hip): in 64 bits the division lands on the VALU and drags the
+    // group counters into vector registers.  ngroups = stream_groups<GEOM.step, GEOM.first>(T), G = groups_per_note(ngroups) and the counter below
+    // are SPELLED here, as in the other four threshold scans (score_c32_prefilter, _prefilter_blk, _prefilter2,
+    // _prefilter2_multi): behind a call the compiler folds them at another point of its pipeline and allocates the
+    // scan's registers differently.  tests/cpp/test_scan_stream.cpp holds this spelling against scan_stream.hpp.
+    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T + (unsigned)GEOM.step - 1u) / (unsigned)GEOM.step));  // >= 2
+    const unsigned G = (ngroups + 63u) / 64u;
     unsigned gleft = G, nnotes = 0, pending = 0;
     unsigned mx = 0;
     GroupNotes notes;
@@ -298,6 +294,7 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
         }
     };
 
+    // FIRST / MAIN ... / LAST (ngroups >= 2); the same walk in score_c32_u8
     prefilter_group<M, PFE, PHASE_FIRST, 0, WIDE>(acc2, sym, sp, tab_even, tab_odd, mx);
     note_group();
     for (unsigned g = 1; g + 1 < ngroups; ++g) {
@@ -314,28 +311,13 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_prefilter(
     }
     unsigned long long hit_groups = notes.finish(nnotes);
 
-    // the flagged groups become candidates for exact re-scoring (outputs are counted from the stream's
-    // first TRUE output row; group 0 completes output 0, group g >= 1 outputs
-    // (g-1)*MP+1 .. g*MP).  Every cell is reported once: the shifted last stream skips
-    // the rows the stream before it owns, idle half-waves report nothing.
+    // the flagged notes become candidates for exact re-scoring.  Every cell is reported once: the shifted last stream
+    // skips the rows the stream before it owns, idle half-waves report nothing.
     const long long first_row = (long long)(o0 - row_begin);
-    const long long own_row = (long long)(stream * T);
-    if (idle)
+    const long long own_row = (long long)(pl.stream * T);
+    if (pl.idle)
         hit_groups = 0;
-    emit_candidates(hit_groups, col, fo, [=](int bit, long long &r0, long long &r1) {
-        const unsigned long long g0 = (unsigned long long)bit * G;
-        unsigned long long g1 = g0 + G;
-        if (g1 > ngroups)
-            g1 = ngroups;
-        const long long i0 = g0 == 0 ? 0 : (long long)((g0 - 1) * MP + 1);
-        long long i1 = (long long)((g1 - 1) * MP + 1);
-        if (i1 > (long long)T)
-            i1 = (long long)T;
-        r0 = first_row + i0;
-        if (r0 < own_row)
-            r0 = own_row;
-        r1 = first_row + i1;
-    });
+    emit_candidates(hit_groups, col, fo, GroupRows<GEOM.step, GEOM.first>{G, ngroups, first_row, own_row, T});
 }
 
 using PrefilterLauncher = hipError_t (*)(dim3 grid, size_t lds_bytes, hipStream_t stream,
@@ -343,17 +325,5 @@ using PrefilterLauncher = hipError_t (*)(dim3 grid, size_t lds_bytes, hipStream_
                                          unsigned long long row_begin, unsigned long long row_end,
                                          unsigned long long T, unsigned long long nstreams,
                                          unsigned td, FusedOut fo);
-
-template <int M, int WIDE = 0>
-hipError_t score_c32_prefilter_launch(dim3 grid, size_t lds_bytes, hipStream_t stream,
-                                      const uint8_t *seq, const unsigned *image, int K,
-                                      unsigned long long row_begin, unsigned long long row_end,
-                                      unsigned long long T, unsigned long long nstreams,
-                                      unsigned td, FusedOut fo)
-{
-    hipLaunchKernelGGL((score_c32_prefilter<M, kScorePF, WIDE>), grid, dim3(kBlock), lds_bytes, stream, seq, image,
-                       K, row_begin, row_end, T, nstreams, td, fo);
-    return hipGetLastError();
-}
 
 }  // namespace lm

@@ -48,8 +48,7 @@ constexpr int kPairPFB = 8;
 // volatile LDS pointer instead -- a lone ds_read_b64 costs 2 cycles, as the protein counters showed -- and drops the
 // padding: the JASPAR batch 22.5 -> 20.6 ms (mean of six interleaved runs; with the padding kept: 22.0;
 // profiles/r03_pair_tail_ab.txt).
-constexpr int prefilter2_mo(int m) { return m | 3; }
-constexpr int prefilter2_ring(int m) { return prefilter2_mo(m) + 1; }   // input rows per group
+// (prefilter2_mo, prefilter2_ring = M' + 1, the input rows per group: scan_stream.hpp)
 constexpr int prefilter2_npair(int m) { return prefilter2_ring(m) / 2; }
 // Two layouts of a DNA pair table (see prefilter2_stride_dw).  Which one a kernel reads travels in its alphabet argument:
 // KA = 5 -- 16-byte slots; KA = kDnaSlot8 -- 8-byte slots.  The multi-motif passes of a batch (LDS-bound, the layout
@@ -204,7 +203,7 @@ __device__ __forceinline__ uint4 prefilter2_biased(uint4 v, const int i, const u
     return v;
 }
 
-// (GroupNotes, the per-stream record of flagged groups, lives in score_prefilter.hpp)
+// (GroupNotes, the per-stream record of flagged groups: scan_stream.hpp)
 
 // Opaque to the optimiser on purpose: LLVM re-associates chains of integer adds and ORs into trees, which keeps table
 // rows and completed sums alive across many super-steps (round 5: hundreds of spilled registers in the unrolled scans).
@@ -543,7 +542,7 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, KA)) void score_c32_pre
     const FusedOut fo_in)
 {
     FusedOut fo = fo_in;
-    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform)
+    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform; the same lines in score_c32_prefilter, score_c32_prefilter_blk)
         const BatchParams bp = fo_in.batch[blockIdx.y];
         image = static_cast<const unsigned *>(bp.table);
         td = bp.td;
@@ -571,14 +570,8 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, KA)) void score_c32_pre
     // lane l of a half-wave reads dword l of the block, i.e. row l >> 3
     constexpr bool LIN = prefilter2_lut_decode(M, KA);
     const int col = LIN ? 4 * (lane & 7) + ((lane >> 3) & 3) : lane & 31;
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    const bool idle = stream >= nstreams;  // re-does the last stream, reports nothing
-    if (idle)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)
-        o0 = row_end - T;
+    const StreamPlace pl = place_stream(row_begin, row_end, T, nstreams);
+    const unsigned long long o0 = pl.o0;
 
     // padded output l covers input rows (o0 - SHIFT) + l .. + MO - 1; the first SHIFT of them
     // carry all-zero weight rows, so rows before the matrix are never loaded (their
@@ -597,19 +590,16 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, KA)) void score_c32_pre
 #pragma unroll
     for (int j = 0; j < NB; ++j)
         blk[j] = 0;
-    // prologue: block 0 (rows in0 .. in0+3; a lane whose row lies before the matrix skips
-    // it) and the next PFB - 1 blocks
-    if (in0 + (long long)(col & 3) >= 0)
-        blk[0] = *reinterpret_cast<const unsigned *>(spq);
-#pragma unroll
-    for (int j = 1; j < PFB; ++j)
-        if (4 * j >= SHIFT || in0 + 4 * j + (long long)(col & 3) >= 0)  // SHIFT > 3: block 1 may start before the matrix too
-            blk[j] = *reinterpret_cast<const unsigned *>(spq + j * 128);
+    block_prologue<NB, PFB, SHIFT>(blk, spq, in0, col & 3);
 
-    // wave-uniform 32-bit bookkeeping (T <= 2^30, score_plan.hip): in 64 bits the division lands on the VALU and
-    // drags the group counters into vector registers
-    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - 2u) / (unsigned)RING + 1u));  // exact: T = q*RING + 2
-    const unsigned G = (ngroups + 63u) / 64u;  // groups per note (= per bit of hit_groups)
+    constexpr StreamGeom GEOM = pair_geom(M);
+    // Wave-uniform 32-bit bookkeeping (T <= 2^30, score_plan.hip): in 64 bits the division lands on the VALU and drags the
+    // group counters into vector registers.  ngroups = stream_groups<GEOM.step, GEOM.first>(T), G = groups_per_note(ngroups) and the counter below
+    // are SPELLED here, as in the other four threshold scans (score_c32_prefilter, _prefilter_blk, _prefilter2,
+    // _prefilter2_multi): behind a call the compiler folds them at another point of its pipeline and allocates the
+    // scan's registers differently.  tests/cpp/test_scan_stream.cpp holds this spelling against scan_stream.hpp.
+    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - (unsigned)GEOM.first) / (unsigned)GEOM.step + 1u));
+    const unsigned G = (ngroups + 63u) / 64u;
     unsigned gleft = G, nnotes = 0;
     unsigned mx[1] = {0};
     GroupNotes notes;
@@ -626,6 +616,7 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, KA)) void score_c32_pre
     unsigned off0, off1;
     FlagSink<1, LIN> sink{mx};
     pair_begin<M, KA, PFB, LIN>(blk, cur, off0, off1, spq, shq, pd);
+    // (FIRST / MAIN ... / LAST with FAR / NEAR: the same walk in score_c32_prefilter2_multi, score_c32_u8_pairs and score_c32_prefilter_blk)
     constexpr unsigned FAR = 2u * RING * 32u, NEAR = RING * 32u;  // (pair_items: the group two groups ahead, where the stream has one)
     pair_items<M, KA, 1, PFB, PHASE_FIRST, 0>(acc, blk, cur, off0, off1, spq, shq, pd, sink, ngroups > 2 ? FAR : NEAR);
     end_group();
@@ -645,27 +636,13 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, KA)) void score_c32_pre
     }
     unsigned long long hit_groups = notes.finish(nnotes);
 
-    // flagged groups -> candidate row ranges (group 0: outputs 0, 1; group g >= 1: outputs
-    // (g-1)*RING + 2 .. g*RING + 1, counted from the stream's first output row)
+    // flagged notes -> candidate row ranges
     const long long first_row = (long long)(o0 - row_begin);
-    const long long own_row = (long long)(stream * T);
-    if (idle)
+    const long long own_row = (long long)(pl.stream * T);
+    if (pl.idle)
         hit_groups = 0;
     __syncthreads();  // the table is done with: its first bytes become emit_candidates' scratch
-    emit_candidates<true>(hit_groups, col, fo, [=](int bit, long long &r0, long long &r1) {
-        const unsigned long long g0 = (unsigned long long)bit * G;
-        unsigned long long g1 = g0 + G;
-        if (g1 > ngroups)
-            g1 = ngroups;
-        const long long i0 = g0 == 0 ? 0 : (long long)((g0 - 1) * RING + 2);
-        long long i1 = (long long)((g1 - 1) * RING + 2);
-        if (i1 > (long long)T)
-            i1 = (long long)T;
-        r0 = first_row + i0;
-        if (r0 < own_row)
-            r0 = own_row;
-        r1 = first_row + i1;
-    }, lds_raw);
+    emit_candidates<true>(hit_groups, col, fo, GroupRows<GEOM.step, GEOM.first>{G, ngroups, first_row, own_row, T}, lds_raw);
 }
 
 // ---- several motifs of one length per pass ------------------------------------------------------
@@ -709,14 +686,8 @@ __global__ __launch_bounds__(kBlock, prefilter2_npair(M) <= 14 ? 4 : 3) void sco
 
     const int lane = threadIdx.x & 63;
     const int col = lane & 31;
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    const bool idle = stream >= nstreams;
-    if (idle)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)
-        o0 = row_end - T;
+    const StreamPlace pl = place_stream(row_begin, row_end, T, nstreams);
+    const unsigned long long o0 = pl.o0;
     const long long in0 = (long long)o0 - SHIFT;
     const unsigned shq = 8u * (col & 3);
     const uint8_t *spq = seq + (in0 + (col & 3)) * 32 + (col >> 2) * 4;
@@ -732,14 +703,11 @@ __global__ __launch_bounds__(kBlock, prefilter2_npair(M) <= 14 ? 4 : 3) void sco
 #pragma unroll
     for (int j = 0; j < NB; ++j)
         blk[j] = 0;
-    if (in0 + (long long)(col & 3) >= 0)
-        blk[0] = *reinterpret_cast<const unsigned *>(spq);
-#pragma unroll
-    for (int j = 1; j < PFB; ++j)
-        if (4 * j >= SHIFT || in0 + 4 * j + (long long)(col & 3) >= 0)  // SHIFT > 3: block 1 may start before the matrix too
-            blk[j] = *reinterpret_cast<const unsigned *>(spq + j * 128);
+    block_prologue<NB, PFB, SHIFT>(blk, spq, in0, col & 3);
 
-    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - 2u) / (unsigned)RING + 1u));
+    constexpr StreamGeom GEOM = pair_geom(M);
+    // (ngroups, G and the counter: spelled as in score_c32_prefilter2 above, see there)
+    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - (unsigned)GEOM.first) / (unsigned)GEOM.step + 1u));
     const unsigned G = (ngroups + 63u) / 64u;
     unsigned gleft = G, nnotes = 0;
     unsigned mx[NM];
@@ -761,6 +729,7 @@ __global__ __launch_bounds__(kBlock, prefilter2_npair(M) <= 14 ? 4 : 3) void sco
     unsigned off0, off1;
     FlagSink<NM> sink{mx};
     pair_begin<M, KM, PFB>(blk, cur, off0, off1, spq, shq, pd);
+    // (FIRST / MAIN ... / LAST with FAR / NEAR: the same walk in score_c32_prefilter2, score_c32_u8_pairs and score_c32_prefilter_blk)
     constexpr unsigned FAR = 2u * RING * 32u, NEAR = RING * 32u;  // (pair_items: the group two groups ahead, where the stream has one)
     pair_items<M, KM, NM, PFB, PHASE_FIRST, 0>(acc, blk, cur, off0, off1, spq, shq, pd, sink, ngroups > 2 ? FAR : NEAR);
     end_group();
@@ -786,26 +755,14 @@ __global__ __launch_bounds__(kBlock, prefilter2_npair(M) <= 14 ? 4 : 3) void sco
         hit_groups[mi] = notes[mi].finish(nnotes);
 
     const long long first_row = (long long)(o0 - row_begin);
-    const long long own_row = (long long)(stream * T);
+    const long long own_row = (long long)(pl.stream * T);
 #pragma unroll
     for (int mi = 0; mi < NM; ++mi) {
         FusedOut fo = fo_in;
         fo.job_key = bps[mi].job_key;
         __syncthreads();  // the tables are done with (first motif) / the scratch is reused (the others)
-        emit_candidates<true>(idle ? 0ull : hit_groups[mi], col, fo, [=](int bit, long long &r0, long long &r1) {
-            const unsigned long long g0 = (unsigned long long)bit * G;
-            unsigned long long g1 = g0 + G;
-            if (g1 > ngroups)
-                g1 = ngroups;
-            const long long i0 = g0 == 0 ? 0 : (long long)((g0 - 1) * RING + 2);
-            long long i1 = (long long)((g1 - 1) * RING + 2);
-            if (i1 > (long long)T)
-                i1 = (long long)T;
-            r0 = first_row + i0;
-            if (r0 < own_row)
-                r0 = own_row;
-            r1 = first_row + i1;
-        }, lds_raw);
+        emit_candidates<true>(pl.idle ? 0ull : hit_groups[mi], col, fo,
+                              GroupRows<GEOM.step, GEOM.first>{G, ngroups, first_row, own_row, T}, lds_raw);
     }
 }
 
@@ -814,27 +771,15 @@ using PrefilterMultiLauncher = hipError_t (*)(dim3 grid, hipStream_t stream, con
                                               unsigned long long row_begin, unsigned long long row_end,
                                               unsigned long long T, unsigned long long nstreams, FusedOut fo);
 
+// (the multi-motif pass sizes its own LDS: NM tables)
 template <int M>
 hipError_t score_c32_prefilter2_multi_launch(dim3 grid, hipStream_t stream, const uint8_t *seq,
                                              unsigned long long row_begin, unsigned long long row_end,
                                              unsigned long long T, unsigned long long nstreams, FusedOut fo)
 {
     constexpr int NM = prefilter2_multi(M);
-    hipLaunchKernelGGL((score_c32_prefilter2_multi<M, NM>), grid, dim3(kBlock),
-                       (size_t)NM * prefilter2_image_dw(M, kDnaMulti) * 4, stream, seq, row_begin, row_end, T, nstreams, fo);
-    return hipGetLastError();
-}
-
-template <int M, int KA = 5>
-hipError_t score_c32_prefilter2_launch(dim3 grid, size_t lds_bytes, hipStream_t stream,
-                                       const uint8_t *seq, const unsigned *image, int K,
-                                       unsigned long long row_begin, unsigned long long row_end,
-                                       unsigned long long T, unsigned long long nstreams,
-                                       unsigned td, FusedOut fo)
-{
-    hipLaunchKernelGGL((score_c32_prefilter2<M, KA>), grid, dim3(kBlock), lds_bytes, stream, seq, image,
-                       K, row_begin, row_end, T, nstreams, td, fo);
-    return hipGetLastError();
+    return launch_scan<score_c32_prefilter2_multi<M, NM>>(grid, (size_t)NM * prefilter2_image_dw(M, kDnaMulti) * 4, stream, seq, row_begin,
+                                                          row_end, T, nstreams, fo);
 }
 
 }  // namespace lm

@@ -161,7 +161,7 @@ constexpr int prefilter_blk_waves(int m)
     return mp <= 16 ? 8 : mp <= 20 ? 6 : mp <= 28 ? 5 : 4;
 }
 
-// Same stream geometry as score_c32_prefilter: T = q*MP + 1 outputs in q + 1 groups of MP steps.
+// Same stream geometry as score_c32_prefilter: one_symbol_geom(M, 1) (scan_stream.hpp).
 template <int M>
 __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_prefilter_blk(
     const uint8_t *__restrict__ seq, const unsigned *__restrict__ image, const int K,
@@ -170,7 +170,7 @@ __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_pref
     const FusedOut fo_in)
 {
     FusedOut fo = fo_in;
-    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform)
+    if (fo_in.batch) {  // multi-job launch: this block's job (wave-uniform; the same lines in score_c32_prefilter, score_c32_prefilter2)
         const BatchParams bp = fo_in.batch[blockIdx.y];
         image = static_cast<const unsigned *>(bp.table);
         td = bp.td;
@@ -202,14 +202,8 @@ __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_pref
 
     const int lane = threadIdx.x & 63;
     const int col = 4 * (lane & 7) + ((lane >> 3) & 3);  // the column this lane accumulates (see the file header)
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    const bool idle = stream >= nstreams;  // re-does the last stream, reports nothing
-    if (idle)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)
-        o0 = row_end - T;
+    const StreamPlace pl = place_stream(row_begin, row_end, T, nstreams);
+    const unsigned long long o0 = pl.o0;
 
     // padded output l covers input rows (o0 - SHIFT) + l .. + MP - 1; the first SHIFT of them carry all-zero weight rows,
     // so rows before the matrix are never loaded (their "symbols" read as 0, a valid table row)
@@ -221,15 +215,19 @@ __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_pref
 #pragma unroll
     for (int i = 0; i < NP; ++i)
         acc2[i] = 0;
-    blk[0] = 0;
-    if (in0 + (long long)brow >= 0)
-        blk[0] = load_block(spq);
 #pragma unroll
-    for (int j = 1; j < NB; ++j)
-        blk[j] = load_block(spq + j * 128);
+    for (int j = 0; j < NB; ++j)
+        blk[j] = 0;
+    block_prologue<NB, NB, SHIFT>(blk, spq, in0, brow);  // the whole ring; SHIFT <= 3: only block 0 can start before the matrix
 
-    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - 1u) / (unsigned)MP + 1u));  // exact: T = q*MP + 1
-    const unsigned G = (ngroups + 63u) / 64u;  // groups per note (= per bit of hit_groups)
+    constexpr StreamGeom GEOM = one_symbol_geom(M, 1);
+    // Wave-uniform 32-bit bookkeeping (T <= 2^30, score_plan.hip): in 64 bits the division lands on the VALU and drags the
+    // group counters into vector registers.  ngroups = stream_groups<GEOM.step, GEOM.first>(T), G = groups_per_note(ngroups) and the counter below
+    // are SPELLED here, as in the other four threshold scans (score_c32_prefilter, _prefilter_blk, _prefilter2,
+    // _prefilter2_multi): behind a call the compiler folds them at another point of its pipeline and allocates the
+    // scan's registers differently.  tests/cpp/test_scan_stream.cpp holds this spelling against scan_stream.hpp.
+    const unsigned ngroups = (unsigned)__builtin_amdgcn_readfirstlane((int)(((unsigned)T - (unsigned)GEOM.first) / (unsigned)GEOM.step + 1u));
+    const unsigned G = (ngroups + 63u) / 64u;
     unsigned gleft = G, nnotes = 0;
     unsigned mx = 0;
     GroupNotes notes;
@@ -249,6 +247,7 @@ __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_pref
     blk_begin_rows<M, 0>(cur, byte_times<0>(sym4, dsb), byte_times<1>(sym4, dsb));
     // `far`: offset of block 0 of the group after next, which the last item of a group requests -- of the NEXT group's where
     // the stream has no such group (a re-read of a block that surely exists instead of 128 bytes past the stream's rows)
+    // (FIRST / MAIN ... / LAST with FAR / NEAR: the same walk in score_c32_prefilter2, _multi and score_c32_u8_pairs)
     constexpr unsigned FAR = 2u * NB * 128u, NEAR = NB * 128u;
     blk_items<M, PHASE_FIRST, 0>(acc2, blk, cur, sym4, spq, mx, tr, dsb, ngroups > 2 ? FAR : NEAR);
     end_group();
@@ -266,37 +265,13 @@ __global__ __launch_bounds__(kBlock, prefilter_blk_waves(M)) void score_c32_pref
     }
     unsigned long long hit_groups = notes.finish(nnotes);
 
-    // flagged groups -> candidate row ranges (group 0: output 0; group g >= 1: outputs (g-1)*MP + 1 .. g*MP, counted from
-    // the stream's first output row)
+    // flagged notes -> candidate row ranges
     const long long first_row = (long long)(o0 - row_begin);
-    const long long own_row = (long long)(stream * T);
-    if (idle)
+    const long long own_row = (long long)(pl.stream * T);
+    if (pl.idle)
         hit_groups = 0;
     __syncthreads();  // the table is done with: its first bytes become emit_candidates' scratch
-    emit_candidates<true>(hit_groups, col, fo, [=](int bit, long long &r0, long long &r1) {
-        const unsigned long long g0 = (unsigned long long)bit * G;
-        unsigned long long g1 = g0 + G;
-        if (g1 > ngroups)
-            g1 = ngroups;
-        const long long i0 = g0 == 0 ? 0 : (long long)((g0 - 1) * MP + 1);
-        long long i1 = (long long)((g1 - 1) * MP + 1);
-        if (i1 > (long long)T)
-            i1 = (long long)T;
-        r0 = first_row + i0;
-        if (r0 < own_row)
-            r0 = own_row;
-        r1 = first_row + i1;
-    }, lds_raw);
-}
-
-template <int M>
-hipError_t score_c32_prefilter_blk_launch(dim3 grid, size_t lds_bytes, hipStream_t stream, const uint8_t *seq, const unsigned *image,
-                                          int K, unsigned long long row_begin, unsigned long long row_end, unsigned long long T,
-                                          unsigned long long nstreams, unsigned td, FusedOut fo)
-{
-    hipLaunchKernelGGL((score_c32_prefilter_blk<M>), grid, dim3(kBlock), lds_bytes, stream, seq, image, K, row_begin, row_end, T,
-                       nstreams, td, fo);
-    return hipGetLastError();
+    emit_candidates<true>(hit_groups, col, fo, GroupRows<GEOM.step, GEOM.first>{G, ngroups, first_row, own_row, T}, lds_raw);
 }
 
 }  // namespace lm

@@ -44,13 +44,7 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_u8(
 
     const int lane = threadIdx.x & 63;
     const int col = lane & 31;
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    if (stream >= nstreams)  // idle half-waves redo the last stream (same bytes, same values)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)    // the last stream is shifted back and overlaps its neighbour
-        o0 = row_end - T;
+    const unsigned long long o0 = place_stream(row_begin, row_end, T, nstreams).o0;  // idle half-waves redo the last stream (same bytes, same values)
 
     const uint8_t *sp = seq + (long long)(o0 - SHIFT) * 32 + col;
     constexpr int PFE = prefilter_lookahead(PF, MP);
@@ -59,6 +53,7 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_u8(
 #pragma unroll
     for (int i = 0; i < NP; ++i)
         acc2[i] = 0;
+    // (the symbol ring zeroed, then the look-ahead: the same lines in score_c32_prefilter)
 #pragma unroll
     for (int j = 0; j < MP; ++j)
         sym[j] = 0;
@@ -72,8 +67,9 @@ __global__ __launch_bounds__(kBlock, 6) void score_c32_u8(
         }
     }
 
-    // group 0 completes output 0, group g >= 1 outputs (g-1)*MP+1 .. g*MP
-    const unsigned long long ngroups = (T + MP - 1) / MP;  // exact: T = q*MP + 1, >= 2
+    // group 0 completes output 0, group g >= 1 outputs (g-1)*MP+1 .. g*MP; FIRST / MAIN ... / LAST as in score_c32_prefilter
+    constexpr StreamGeom GEOM = one_symbol_geom(M, WIDE);
+    const unsigned long long ngroups = stream_groups<GEOM.step, GEOM.first>(T);  // >= 2
     uint8_t *op = out + (o0 - row_begin) * 32 + col;
     unsigned mx = 0;
     prefilter_group<M, PFE, PHASE_FIRST, 1, WIDE>(acc2, sym, sp, tab_even, tab_odd, mx, op, wrap_mask);
@@ -115,13 +111,7 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, 5)) void score_c32_u8_p
     const int lane = threadIdx.x & 63;
     constexpr bool LIN = prefilter2_lut_decode(M, 5);  // lane l of a half-wave on dword l of a block (score_prefilter2.hpp)
     const int col = LIN ? 4 * (lane & 7) + ((lane >> 3) & 3) : lane & 31;
-    unsigned long long stream =
-        ((unsigned long long)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6)) * 2 + (lane >> 5);
-    if (stream >= nstreams)  // idle half-waves redo the last stream (same bytes, same values)
-        stream = nstreams - 1;
-    unsigned long long o0 = row_begin + stream * T;
-    if (o0 + T > row_end)
-        o0 = row_end - T;
+    const unsigned long long o0 = place_stream(row_begin, row_end, T, nstreams).o0;  // idle half-waves redo the last stream (same bytes, same values)
 
     const long long in0 = (long long)o0 - SHIFT;  // first input row of the stream (padding rows: weight 0)
     const unsigned shq = 8u * (col & 3);
@@ -136,15 +126,12 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, 5)) void score_c32_u8_p
 #pragma unroll
     for (int j = 0; j < NB; ++j)
         blk[j] = 0;
-    if (in0 + (long long)(col & 3) >= 0)
-        blk[0] = *reinterpret_cast<const unsigned *>(spq);
-#pragma unroll
-    for (int j = 1; j < PFB; ++j)
-        if (4 * j >= SHIFT || in0 + 4 * j + (long long)(col & 3) >= 0)  // SHIFT > 3: block 1 may start before the matrix too
-            blk[j] = *reinterpret_cast<const unsigned *>(spq + j * 128);
+    block_prologue<NB, PFB, SHIFT>(blk, spq, in0, col & 3);
 
     // group 0 completes rows 0 and 1, group g >= 1 rows (g-1)*RING + 2 .. g*RING + 1
-    const unsigned long long ngroups = (T - 2) / RING + 1;  // exact: T = q*RING + 2
+    // (FIRST / MAIN ... / LAST with FAR / NEAR: the same walk in score_c32_prefilter2, _multi and score_c32_prefilter_blk)
+    constexpr StreamGeom GEOM = pair_geom(M);
+    const unsigned long long ngroups = stream_groups<GEOM.step, GEOM.first>(T);
     uint8_t *op = out + (o0 - row_begin) * 32 + col;
     const PairDecode pd = pair_decode_setup<prefilter2_so(M), LIN>();
     PairRows<NP> cur;
@@ -165,22 +152,11 @@ __global__ __launch_bounds__(kBlock, prefilter2_waves(M, 5)) void score_c32_u8_p
     }
 }
 
-// Host-side launch shims of the two u8 kernels (one type: K is ignored by the pair scan).
+// Launcher type of the two u8 kernels (one type: the pair scan takes no K, hence its adapter).
 using ScoreU8Launcher = hipError_t (*)(dim3 grid, size_t lds_bytes, hipStream_t stream, const uint8_t *seq,
                                        const unsigned *image, int K, unsigned long long row_begin,
                                        unsigned long long row_end, unsigned long long T,
                                        unsigned long long nstreams, uint8_t *out, unsigned wrap_mask);
-
-template <int M, int WIDE = 0>
-hipError_t score_c32_u8_launch(dim3 grid, size_t lds_bytes, hipStream_t stream, const uint8_t *seq,
-                               const unsigned *image, int K, unsigned long long row_begin,
-                               unsigned long long row_end, unsigned long long T, unsigned long long nstreams,
-                               uint8_t *out, unsigned wrap_mask)
-{
-    hipLaunchKernelGGL((score_c32_u8<M, kScorePF, WIDE>), grid, dim3(kBlock), lds_bytes, stream, seq, image, K, row_begin,
-                       row_end, T, nstreams, out, wrap_mask);
-    return hipGetLastError();
-}
 
 template <int M>
 hipError_t score_c32_u8_pairs_launch(dim3 grid, size_t lds_bytes, hipStream_t stream, const uint8_t *seq,
@@ -189,9 +165,7 @@ hipError_t score_c32_u8_pairs_launch(dim3 grid, size_t lds_bytes, hipStream_t st
                                      unsigned long long nstreams, uint8_t *out, unsigned wrap_mask)
 {
     (void)K;
-    hipLaunchKernelGGL((score_c32_u8_pairs<M>), grid, dim3(kBlock), lds_bytes, stream, seq, image, row_begin,
-                       row_end, T, nstreams, out, wrap_mask);
-    return hipGetLastError();
+    return launch_scan<score_c32_u8_pairs<M>>(grid, lds_bytes, stream, seq, image, row_begin, row_end, T, nstreams, out, wrap_mask);
 }
 
 }  // namespace lm
