@@ -826,7 +826,7 @@ int lm_hip_merge_threshold(lm_hip_ctx *ctx, lm_hip_comm *comm, const lm_hip_coor
 /* ---- host-pointer convenience forms (synchronous, PCIe both ways) ---------- */
 
 /* Exactly what a Rust shim can obtain from &StripedSequence / &DenseMatrix / &mut StripedScores: pageable host
- * matrices in, pageable host matrices out (csrc/hostptr.hip).  No context argument: every calling host thread is given
+ * matrices in, pageable host matrices out (csrc/hostptr.hip; lanes: host_lane.hip, large calls: host_pipe.hip).  No context argument: every calling host thread is given
  * a lane of its own (context + stream, persistent staging, a cache of device PSSM tables keyed on the weights), so
  * threads overlap.  Lanes sit on ONE device unless told otherwise: $LM_HIP_DEVICE (read once per process; must name a
  * usable ordinal), else the HIP device current in the thread that made the first host-pointer call -- so a job of one

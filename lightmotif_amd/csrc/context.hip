@@ -3,7 +3,8 @@
 //   pssm.hip       lm_hip_pssm_*: the device image of a scoring matrix, built by pssm_tables.hpp (f32 tables, prefilter images)
 //   score_api.hip  Score / Maximum / Threshold on device pointers, the fused and batched scans
 //   handles.hip    resident StripedSequence / StripedScores handles, host -> device ingest
-//   hostptr.hip    the host-pointer entry points a reference-side shim binds
+//   hostptr.hip    the host-pointer entry points a reference-side shim binds (host_lane.hip: the per-thread lanes,
+//                  host_pipe.hip: the tile pipeline of large calls, host_cost.hip: the Dispatch::Hip cost model)
 //   comm.hip       row-sharded jobs over RCCL
 #include <algorithm>
 #include <sys/mman.h>

@@ -1,6 +1,6 @@
 """The literal drop-in path: the host-pointer entry points a reference-side shim binds --
 `lm_hip_score_f32`, `lm_hip_argmax_f32`, `lm_hip_max_f32`, `lm_hip_threshold_f32`, `lm_hip_score_u8` -- against
-the oracle, bit for bit, over every route inside `csrc/hostptr.hip`: zero-copy (tiny), copy (small), the tile
+the oracle, bit for bit, over every route inside `csrc/hostptr.hip` (lanes: `host_lane.hip`, tiles: `host_pipe.hip`): zero-copy (tiny), copy (small), the tile
 pipeline (large, several tiles, ragged last tile), the piecewise fallback when the pipeline is taken, row ranges,
 `out_stride != cols`, column counts other than 32, protein, the per-thread PSSM cache and its eviction, and host
 threads calling in concurrently (pwm/mod.rs:640-648, scores.rs:181-213, avx2.rs:889-904, scan.rs:174-178)."""
@@ -530,3 +530,97 @@ def test_kept_scores_with_host_threads():
     assert not errors, errors
     # (a lane taken over from an exited thread may owe an lm_hip_host_trim its staging: its first score call then keeps nothing)
     assert all(2 * (iters - 1) <= r <= 2 * iters for r in reused) and len(reused) == nthreads, reused
+
+
+# ---- kept scores: the transitions between "kept", "tracked" and "forgotten" (k = 5, M = 15, 32 columns) -----------------
+
+def kept_case(length, seed):
+    rng = np.random.default_rng(seed)
+    s = striped(rng, length, 32, 5, 15)
+    p = aligned(random_pssm(rng, 15, 5, "ties"))
+    want, _ = co.score_rows(s, p)
+    return s, p, co.argmax(want, 32)
+
+
+def reuse_count():
+    n = C.c_size_t(0)
+    assert _ffi.lib().lm_hip_host_reuse_count(C.byref(n)) == 0, _ffi.last_error()
+    return n.value
+
+
+@pytest.mark.parametrize("length,survives", [
+    (90_001, 0),   # copy path (360 KB of scores): the kept matrix sits in the lane's staging, which the trim releases
+    (2_000, 1),    # zero-copy (8 KB): it sits in the lane's pinned block, which is not staging and survives the trim
+])
+def test_kept_scores_across_a_host_trim(length, survives):
+    """`lm_hip_host_trim` on the thread that keeps a matrix: a copied matrix is gone with its staging buffer (the next
+    argmax uploads and still answers for the host matrix), a zero-copy one is still there; either way the next score call
+    keeps its result again."""
+    L = _ffi.lib()
+    s, p, best = kept_case(length, 1000 + length)
+    assert L.lm_hip_host_reuse_scores(1) == 0
+    try:
+        out, _, _ = host_score(s, p, 5, 0, s.rows)
+        c0 = reuse_count()
+        assert L.lm_hip_host_trim() == 0, _ffi.last_error()
+        assert host_argmax(out, s.rows, 32, 32)[0] == best
+        assert reuse_count() == c0 + survives
+        out, _, _ = host_score(s, p, 5, 0, s.rows)
+        assert host_argmax(out, s.rows, 32, 32)[0] == best
+        assert reuse_count() == c0 + survives + 1
+    finally:
+        L.lm_hip_host_reuse_scores(0)
+
+
+@pytest.mark.parametrize("length", [90_001, 2_000])
+def test_kept_scores_survive_a_rejected_score_call(length):
+    """A score call turned away for its arguments (rows narrower than the columns) has not touched the lane's staging:
+    what the call before it left is still kept."""
+    L = _ffi.lib()
+    s, p, best = kept_case(length, 2000 + length)
+    assert L.lm_hip_host_reuse_scores(1) == 0
+    try:
+        out, _, _ = host_score(s, p, 5, 0, s.rows)
+        c0 = reuse_count()
+        junk = np.zeros((s.rows, 32), np.float32)
+        orow, omi = C.c_size_t(0), C.c_size_t(0)
+        st = L.lm_hip_score_f32(s.data.ctypes.data, s.data.shape[0], s.stride, 32, s.wrap, s.length, p.ctypes.data, 15, p.shape[1], 5,
+                                0, s.rows, junk.ctypes.data, 16, C.byref(orow), C.byref(omi))
+        assert st == _ffi.ERR_BAD_ARGS and not junk.any()
+        assert host_argmax(out, s.rows, 32, 32)[0] == best
+        assert reuse_count() == c0 + 1
+    finally:
+        L.lm_hip_host_reuse_scores(0)
+
+
+def test_kept_scores_do_not_pass_to_the_next_thread():
+    """A lane whose thread has exited serves the next new thread -- without what the first thread's call left on it: the
+    second thread starts at a reuse count of 0, its argmax of the SAME host matrix uploads, and only its own score call is
+    kept."""
+    L = _ffi.lib()
+    s, p, best = kept_case(90_001, 3000)
+    got = {}
+
+    def first():
+        got["out"] = host_score(s, p, 5, 0, s.rows)[0]
+
+    def second():
+        out = got["out"]
+        got["count_at_start"] = reuse_count()
+        got["best_uploaded"] = host_argmax(out, s.rows, 32, 32)[0]
+        got["count_after_upload"] = reuse_count()
+        out2, _, _ = host_score(s, p, 5, 0, s.rows)
+        got["best_kept"] = host_argmax(out2, s.rows, 32, 32)[0]
+        got["count_after_own_score"] = reuse_count()
+
+    assert L.lm_hip_host_reuse_scores(1) == 0
+    try:
+        for work in (first, second):   # one after the other: the second starts after the first has exited
+            th = threading.Thread(target=work)
+            th.start()
+            th.join()
+    finally:
+        L.lm_hip_host_reuse_scores(0)
+    got.pop("out")
+    assert got["count_at_start"] == 0 and got["best_uploaded"] == best and got["count_after_upload"] == 0, got
+    assert got["best_kept"] == best and got["count_after_own_score"] == 1, got

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Shape of the host-pointer tile pipeline (csrc/hostptr.hip), swept on one box with the -DLM_HIP_DEV_SWITCHES build:
+# Shape of the host-pointer tile pipeline (csrc/host_pipe.hip), swept on one box with the -DLM_HIP_DEV_SWITCHES build:
 #   python tools/build_variant.py dev -DLM_HIP_DEV_SWITCHES && bash tools/hostpipe_sweep.sh > profiles/r04_hostpipe_sweep.txt
 # Each line: tile MB / pinned ring slots / copier threads -> 1 Gbp x M = 20 through lm_hip_score_f32, with the
 # pipeline's own account of where its threads waited (LM_HIP_PIPE_TRACE).
