@@ -196,17 +196,13 @@ static int launch_count_symbols(lm_hip_ctx *ctx, const lm_hip_seq *seq, const un
     const unsigned long long nscan = (n + kScanTile - 1) / kScanTile;
     if (nscan >> 31)
         return fail(LM_HIP_ERR_CAPACITY, "count_symbols: %llu blocks of %zu rows are beyond the scan's grid", g.nb, T);
-    const size_t off_scanned = (size_t)((n * 4 + 15) / 16 * 16);
-    const size_t off_tiles = off_scanned + (size_t)n * 8;
-    const size_t off_total = off_tiles + (size_t)nscan * 8;
-    const size_t off_prefix = off_total + 16;
+    const size_t off_prefix = hits::scan_layout(n).bytes;
     const size_t off_out = off_prefix + (records + 1) * seq->k * 8;
     LM_TRY(ctx->scratch.reserve(off_out + records * seq->k * 8));
     char *block = static_cast<char *>(ctx->scratch.ptr);
-    unsigned *table = reinterpret_cast<unsigned *>(block);
-    unsigned long long *scanned = reinterpret_cast<unsigned long long *>(block + off_scanned);
-    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(block + off_tiles);
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(block + off_total);
+    const ScanArrays scan = carve_scan_u32(block, n);
+    unsigned *table = scan.counts;
+    unsigned long long *scanned = scan.offsets, *tiles = scan.tiles;
     unsigned long long *prefix = reinterpret_cast<unsigned long long *>(block + off_prefix);
     unsigned long long *d_out = reinterpret_cast<unsigned long long *>(block + off_out);
 
@@ -217,7 +213,7 @@ static int launch_count_symbols(lm_hip_ctx *ctx, const lm_hip_seq *seq, const un
     LM_HIP_TRY(hipGetLastError());
     ctx->last_kernel = "count_blocks";
     scan_timer_end(ctx, ctx->stream);
-    LM_TRY(launch_scan_u32(ctx, table, n, scanned, tiles, total));
+    LM_TRY(launch_scan_u32(ctx, scan, n));
     scan_timer_mark(ctx, ctx->stream, 2);
     const unsigned long long n_offsets = (unsigned long long)records + 1, cells = (unsigned long long)records * seq->k;
     if (seq->length / n_offsets >= kCountSparseBases)

@@ -29,6 +29,13 @@
 // `shift` is chosen from the hit density so that a bucket holds ~1 record on
 // average; a bucket never holds more records than it has cells (2^shift), which bounds
 // step 4 at 8 x (cells of the batch) comparisons whatever the distribution of hits.
+//
+// The host half is three steps.  hits_plan.hpp (pure arithmetic, tested on the CPU by tests/cpp/test_hits_plan.cpp)
+// chooses the form -- Short, Buckets or Sorted -- and lays out ctx->scratch2 and the pinned staging block as named
+// regions; `enqueue` launches the kernels of that plan; `deliver` reads counters and job starts, decides the outcome and
+// fills the caller's arrays.  Two entry points: order_hits_speculative (enqueued behind the scans before the host knows
+// the count; reports Done, Overflow or TooCoarse with the counts) and order_hits_counted (the count is known; nothing
+// to report but the list).
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -41,7 +48,8 @@ namespace lm {
 
 namespace {
 
-constexpr unsigned long long kLowMask = (1ull << 40) - 1;
+using namespace hits;  // constants, geometry and layouts: hits_plan.hpp
+static_assert(kBlock == kPlanBlock && sizeof(HitRecord) == kRecordBytes, "hits_plan.hpp plans for these kernels");
 
 __device__ __forceinline__ unsigned long long bucket_of(unsigned long long key, int shift,
                                                         unsigned long long nb)
@@ -218,17 +226,7 @@ __global__ void hits_job_starts(const unsigned long long njobs, const unsigned l
 //   * the list's counters {hits, candidates} live there as well: the scatter kernel leaves a copy for the ranking kernel,
 //     which clears the originals -- the next scan starts without a head block copied in, its job an argument of the
 //     re-scoring kernel.
-constexpr unsigned long long kShortRecords = 40960;  // expected records (the previous call's count + 25 %) up to which a list is "short"
-constexpr int kShortBuckets = 10496;                 // >= kShortRecords / 4 + 1 (bucket_geometry), a multiple of kBlock; 41 KB of LDS
-constexpr size_t kShortTiles = kShortBuckets / kScanTile + 1;
-// ctx->d_short: counts | cursors | tiles (zero for ever: one "tile" per kScanTile buckets, see bucket_start) | offsets |
-// the list's counters (zero between calls) | their copy for the ranking kernel, which clears the originals
-constexpr size_t kShortOffCursors = kShortBuckets * 4, kShortOffTiles = 2 * kShortOffCursors,
-                 kShortOffOffsets = kShortOffTiles + 128,
-                 kShortOffCounters = (kShortOffOffsets + (kShortBuckets + 1) * 8 + 255) / 256 * 256,  // {hits, candidates}: a line of their own
-                 kShortOffCopy = kShortOffCounters + 256, kShortOffTicket = kShortOffCopy + 128,  // (the ticket of hits_rank_emit's last workgroup)
-                 kShortBytes = kShortOffCopy + 256;
-static_assert(kShortTiles * 8 <= 128 && kShortBuckets % kBlock == 0 && kShortRecords / 4 + 1 <= kShortBuckets, "layout of the short form");
+// (kShortRecords, kShortBuckets and the layout of ctx->d_short: hits_plan.hpp)
 
 __global__ __launch_bounds__(kBlock) void hits_short_scatter(
     const HitRecord *__restrict__ hits, const unsigned long long *__restrict__ count_ptr, const unsigned long long cap,
@@ -280,31 +278,6 @@ __global__ __launch_bounds__(kBlock) void hits_short_scatter(
         grouped[pre[b] + atomicAdd(&cursors[b], 1u)] = r;
     }
 }
-
-// bucket geometry of order_hits for `sized_for` expected records (one place: the re-scoring kernel counts with it)
-void bucket_geometry(unsigned long long sized_for, size_t njobs, unsigned long long max_low, int *shift_out,
-                     unsigned long long *nb_out)
-{
-    // ~1 record per bucket on average; at most 2^26 buckets.  (Ranking is quadratic in the bucket
-    // size and the density is far from uniform across jobs: in the JASPAR batch a length-4 motif
-    // has 150 x the average hit density; at 8 records per average bucket its buckets held 2 800
-    // records and hits_rank_emit took 7 ms of the batch's 47.)
-    int shift = 5;
-    const long double universe = (long double)max_low * (long double)njobs;
-    while (shift < 40 && ((long double)(1ull << shift) * (long double)sized_for < 1.0L * universe))
-        ++shift;
-    while (shift < 40 && (((max_low - 1) >> shift) + 1) * njobs > (1ull << 26))
-        ++shift;
-    // short lists (one motif at p = 1e-5 leaves ~10^4 hits per Gbp): four records per bucket keep the histogram small
-    // (<= kShortBuckets: the short form above; three tiles of the single-launch scan otherwise), and ranking 4 x 4 keys
-    // costs nothing
-    if (sized_for <= kShortRecords && njobs == 1 && shift + 2 < 40)
-        shift += 2;
-    *shift_out = shift;
-    *nb_out = ((max_low - 1) >> shift) + 1;
-}
-
-constexpr unsigned long long kSortFrom = 1ull << 17;  // expected records from which the list is radix-sorted
 
 __global__ __launch_bounds__(kBlock) void hits_split(const HitRecord *__restrict__ hits,
                                                      const unsigned long long *__restrict__ count_ptr,
@@ -398,19 +371,311 @@ __global__ void hits_sorted_starts(const unsigned long long *__restrict__ keys,
     starts[j] = lo;
 }
 
-size_t align16(size_t x) { return (x + 15) / 16 * 16; }
+// ---- host: plan (hits_plan.hpp) -> enqueue -> deliver --------------------------------------------------------------
+
+// the regions of a plan as pointers into ctx->scratch2, ctx->d_short and the pinned staging block
+struct Buffers {
+    char *base, *pin;
+    // Short: histogram, offsets and the (zero) tiles live in the context, with the cursors; otherwise in the work area
+    unsigned *counts, *cursors;
+    unsigned long long *offsets, *tiles;
+    unsigned long long *header;  // pinned: the raw counters {hits, candidates}
+    unsigned *abort_flag;        // pinned
+    void *pre_out;               // pinned: head of the result
+    float *pre_values;
+    unsigned long long *starts;      // of the ordering: pinned when speculative and the result's own, else on the device
+    unsigned long long *seg_starts;  // of the segment pass: pinned when speculative
+    void *d_out;
+    float *d_values;
+    lm_hip_set_hit *d_set;
+    // Short with option "poll_done": the word hits_rank_emit's last workgroup raises, its ticket, the value to wait for
+    unsigned *done_ticket = nullptr, *done_flag = nullptr;
+    unsigned generation = 0;
+};
+
+template <class T>
+T *at(char *block, const Region &r) { return reinterpret_cast<T *>(block + r.off); }
+
+Buffers carve(lm_hip_ctx *ctx, const Plan &p, bool speculative, Output output)
+{
+    Buffers b{};
+    b.base = static_cast<char *>(ctx->scratch2.ptr);
+    b.pin = pinned_at<char>(ctx, kPinHitStaging, 0);  // (the counted form reads back through kPinHitReadback, the same bytes)
+    if (p.form == Form::Short) {
+        char *sb = reinterpret_cast<char *>(ctx->d_short);
+        b.counts = reinterpret_cast<unsigned *>(sb);
+        b.cursors = b.counts + kShortBuckets;
+        b.tiles = reinterpret_cast<unsigned long long *>(sb + kShortOffTiles);
+        b.offsets = reinterpret_cast<unsigned long long *>(sb + kShortOffOffsets);
+    } else {
+        b.counts = at<unsigned>(b.base, p.buckets.counts);
+        b.offsets = at<unsigned long long>(b.base, p.buckets.offsets);
+        b.tiles = at<unsigned long long>(b.base, p.buckets.tiles);
+    }
+    b.header = reinterpret_cast<unsigned long long *>(b.pin);
+    b.abort_flag = reinterpret_cast<unsigned *>(b.pin + Plan::p_abort);
+    b.pre_out = b.pin + p.p_out;
+    b.pre_values = reinterpret_cast<float *>(b.pin + p.p_values);
+    unsigned long long *pin_starts = reinterpret_cast<unsigned long long *>(b.pin + Plan::p_starts);
+    // with a segment pass the ordering's own starts stay on the device (unused); the starts of the compacted list take their place
+    b.starts = speculative && output != Output::Records ? pin_starts : at<unsigned long long>(b.base, p.starts);
+    b.seg_starts = speculative ? pin_starts : at<unsigned long long>(b.base, p.seg_starts);
+    b.d_out = b.base + p.out.off;
+    b.d_values = at<float>(b.base, p.values);
+    b.d_set = at<lm_hip_set_hit>(b.base, p.seg_out);
+    // short form, option "poll_done" = 1: the end of the call is polled (hits_rank_emit's last workgroup; the word sits in the
+    // zeroed head of the staging block, the ticket next to the context's counters) instead of waited for on the stream.
+    // 2.6-4.4 us less per call when nothing synchronises behind it -- and ~13 us MORE when the caller follows the call with a
+    // device synchronisation of its own, which then finds the ranking kernel still retiring and pays a full wake-up
+    // (bench.py's protocol does: 0.252 -> 0.265 ms).  Hence off unless asked for (profiles/r06_poll_done_ab.txt).
+    if (p.form == Form::Short && speculative && ctx->poll_done) {
+        b.done_ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ctx->d_short) + kShortOffTicket);
+        b.done_flag = reinterpret_cast<unsigned *>(b.pin + Plan::p_done);
+        b.generation = next_generation(ctx->short_generation);
+    }
+    return b;
+}
+
+// hipLaunchKernelGGL of KERNEL<0 | 1 | 2> by the output kind
+#define LM_LAUNCH_BY_OUTPUT(KERNEL, output, ...)                                   \
+    do {                                                                           \
+        if ((output) == Output::Coords)                                            \
+            hipLaunchKernelGGL(KERNEL<0>, __VA_ARGS__);                            \
+        else if ((output) == Output::Records)                                      \
+            hipLaunchKernelGGL(KERNEL<2>, __VA_ARGS__);                            \
+        else                                                                       \
+            hipLaunchKernelGGL(KERNEL<1>, __VA_ARGS__);                            \
+    } while (0)
+
+// the kernels of a plan, on ctx->stream
+int enqueue(lm_hip_ctx *ctx, const Plan &p, const Buffers &b, const HitList &list, const HitShape &shape, bool speculative,
+            const ShortOrder *so, const SegmentCut *cut, size_t sort_temp)
+{
+    hipStream_t st = ctx->stream;
+    const dim3 grid(p.grid), block(kBlock);
+    const unsigned long long njobs = shape.njobs, cols = shape.cols, cap = list.cap;
+    const unsigned long long *d_counters = list.d_counters;
+    // Coords write coords + values, the other two kinds whole 16-byte entries through `out_hits`
+    lm_hip_coords *coords = shape.output == Output::Coords ? static_cast<lm_hip_coords *>(b.d_out) : nullptr;
+    float *values = shape.output == Output::Coords ? b.d_values : nullptr;
+    lm_hip_hit *out_hits = shape.output == Output::Coords ? nullptr : static_cast<lm_hip_hit *>(b.d_out);
+    unsigned long long *header = speculative ? b.header : nullptr;
+    if (p.form == Form::Sorted) {
+        unsigned long long *keys_in = at<unsigned long long>(b.base, p.sort.keys_in), *keys_out = at<unsigned long long>(b.base, p.sort.keys_out);
+        float *vals_in = at<float>(b.base, p.sort.vals_in), *vals_out = at<float>(b.base, p.sort.vals_out);
+        hipLaunchKernelGGL(hits_split, grid, block, 0, st, list.d_hits, d_counters, cap, p.n_sort, keys_in, vals_in,
+                           speculative ? b.abort_flag : static_cast<unsigned *>(nullptr));
+        LM_HIP_TRY(hipGetLastError());
+        size_t tb = sort_temp;
+        LM_HIP_TRY(rocprim::radix_sort_pairs(b.base + p.sort.temp.off, tb, keys_in, keys_out, vals_in, vals_out, (size_t)p.n_sort, 0u,
+                                             (unsigned)p.end_bit, st));
+        LM_LAUNCH_BY_OUTPUT(hits_sorted_emit, shape.output, grid, block, 0, st, keys_out, vals_out, d_counters, cap, p.n_sort, cols,
+                            coords, values, out_hits, b.pre_out, b.pre_values, p.order_pre, header);
+        hipLaunchKernelGGL(hits_sorted_starts, dim3(p.starts_grid), dim3(256), 0, st, keys_out, d_counters, cap, p.n_sort, njobs, b.starts);
+        LM_HIP_TRY(hipGetLastError());
+    } else {
+        const bool short_form = p.form == Form::Short;
+        HitRecord *grouped = at<HitRecord>(b.base, p.buckets.grouped);
+        const unsigned long long *rank_counters = short_form ? so->counters_copy : d_counters;
+        if (short_form) {  // the re-scoring kernel has counted
+            hipLaunchKernelGGL(hits_short_scatter, grid, block, 0, st, list.d_hits, d_counters, cap, p.shift, (unsigned)p.nb, b.counts,
+                               b.cursors, b.offsets, grouped, so->counters_copy);
+        } else {
+            LM_HIP_TRY(hipMemsetAsync(b.counts, 0, p.buckets.counts.bytes, st));  // whole 256-B units: one fill kernel
+            hipLaunchKernelGGL(hits_bucket_count, grid, block, 0, st, list.d_hits, d_counters, cap, p.shift, p.nb, b.counts);
+            LM_TRY(launch_scan_u32(ctx, b.counts, p.nbuckets, b.offsets, b.tiles, at<unsigned long long>(b.base, p.total)));
+            hipLaunchKernelGGL(hits_bucket_scatter, grid, block, 0, st, list.d_hits, d_counters, cap, p.shift, p.nb, b.offsets, b.tiles,
+                               b.counts, grouped);
+        }
+        LM_LAUNCH_BY_OUTPUT(hits_rank_emit, shape.output, grid, block, 0, st, grouped, rank_counters, cap, p.shift, p.nb, p.nbuckets,
+                            b.offsets, b.tiles, cols, coords, values, out_hits, p.max_bucket, b.abort_flag, b.pre_out, b.pre_values,
+                            p.order_pre, njobs, p.inline_starts ? b.starts : nullptr, p.inline_starts ? header : nullptr,
+                            short_form ? b.counts : nullptr, b.cursors, short_form ? so->counters : nullptr, b.done_ticket, b.done_flag,
+                            b.generation);
+        if (!p.inline_starts)
+            hipLaunchKernelGGL(hits_job_starts, dim3(p.starts_grid), dim3(256), 0, st, njobs, p.nb, p.nbuckets, d_counters, cap, b.offsets,
+                               b.tiles, b.starts, header);
+        LM_HIP_TRY(hipGetLastError());
+    }
+    if (cut)  // drop the windows that leave their record, make the others record-relative, per-job starts anew (seqset.hip)
+        LM_TRY(launch_segment_cut(st, static_cast<const HitRecord *>(b.d_out), d_counters, p.form == Form::Sorted ? p.n_sort : p.room, njobs,
+                                  *cut, p.seg_grid, at<unsigned>(b.base, p.seg_counts), b.seg_starts, b.d_set,
+                                  static_cast<lm_hip_set_hit *>(b.pre_out), p.pre));
+    scan_timer_mark(ctx, st, 3);  // (time_scan) behind the ordering kernels
+    return LM_HIP_OK;
+}
+
+// What the kernels left, into host arrays for the caller.  Speculative: ONE synchronisation (or the polled word), the
+// counters decide the outcome, the head of the list is in the staging block already and only a long list's remainder is
+// copied from the device.  Counted: starts | records | values in one pinned block copy when they are few, else straight
+// into the caller's arrays.  With a segment pass the list is the compacted one and its length the last of its starts.
+int deliver(lm_hip_ctx *ctx, const Plan &p, const Buffers &b, const HitList &list, const HitShape &shape, unsigned long long count,
+            HitOutput *out, SpeculativeOrder *spec)
+{
+    hipStream_t st = ctx->stream;
+    const bool records = shape.output == Output::Records;
+    const size_t njobs = shape.njobs, starts_bytes = (njobs + 1) * 8;
+    static_assert(sizeof(size_t) == 8, "job offsets are read back as 64-bit values");
+    // 1. counters and starts
+    if (spec) {
+        // the ranking kernel's last workgroup raises the word behind everything it and the others wrote
+        const bool seen = b.done_flag && poll_generation(b.done_flag, b.generation, 1u << 23);  // bounded: a kernel that never gets there is caught below
+        if (!seen || ctx->scan_timed)  // (option "time_scan": the events behind the kernels are read next -- they must have completed)
+            LM_HIP_TRY(hipStreamSynchronize(st));
+        if (p.form == Form::Short)
+            ctx->short_dirty = false;  // both kernels ran: counts and cursors are zero again
+        spec->hits = b.header[0];
+        spec->candidates = b.header[1];
+        // 2. the outcome
+        if (spec->hits > list.cap || spec->candidates > list.cand_cap) {
+            spec->outcome = SpeculativeOrder::Overflow;
+            return LM_HIP_OK;
+        }
+        if (*b.abort_flag) {
+            spec->outcome = SpeculativeOrder::TooCoarse;
+            return LM_HIP_OK;
+        }
+        count = spec->hits;
+        if (count == 0)
+            return LM_HIP_OK;
+        memcpy(out->job_start.data(), b.pin + Plan::p_starts, starts_bytes);
+    } else if (records) {
+        LM_HIP_TRY(hipMemcpyAsync(out->job_start.data(), b.seg_starts, starts_bytes, hipMemcpyDeviceToHost, st));
+        LM_HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (records) {
+        count = out->job_start[njobs];
+        if (count > p.room)
+            return fail(LM_HIP_ERR_HIP, "fused threshold: the segment pass reports %llu of %llu hits", count, p.room);
+        if (count == 0)
+            return LM_HIP_OK;
+    }
+    // 3. the caller's arrays
+    const size_t rec_bytes = records ? sizeof(lm_hip_set_hit) : p.rec_bytes;
+    const char *d_list = records ? reinterpret_cast<const char *>(b.d_set) : static_cast<const char *>(b.d_out);
+    ResultArray<char> host((size_t)count * rec_bytes);
+    ResultArray<float> host_values;
+    if (shape.output == Output::Coords)
+        host_values.p = static_cast<float *>(result_alloc(count * sizeof(float)));
+    if (!host.p || (shape.output == Output::Coords && !host_values.p))
+        return fail(LM_HIP_ERR_OOM, "fused threshold: cannot allocate %llu hits on the host", count);
+    // 4. the head from the staging block
+    const unsigned long long have = spec ? std::min(count, p.pre) : 0;
+    memcpy(host.p, b.pin + p.p_out, have * rec_bytes);
+    if (host_values.p)
+        memcpy(host_values.p, b.pin + p.p_values, have * sizeof(float));
+    // 5. the rest from the device
+    hipError_t e = hipSuccess;
+    if (!spec && !records) {
+        if (p.readback_pinned) {
+            e = hipMemcpyAsync(b.pin, b.base + p.starts.off, p.readback_bytes, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(st);
+            if (e == hipSuccess) {
+                memcpy(out->job_start.data(), b.pin, starts_bytes);
+                memcpy(host.p, b.pin + (p.out.off - p.starts.off), count * rec_bytes);
+                if (host_values.p)
+                    memcpy(host_values.p, b.pin + (p.values.off - p.starts.off), count * sizeof(float));
+            }
+        } else {
+            e = hipMemcpyAsync(out->job_start.data(), b.starts, starts_bytes, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipMemcpyAsync(host.p, d_list, count * rec_bytes, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess && host_values.p)
+                e = hipMemcpyAsync(host_values.p, b.d_values, count * sizeof(float), hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess)
+                e = hipStreamSynchronize(st);
+        }
+        if (e != hipSuccess)
+            return fail(LM_HIP_ERR_HIP, "fused threshold: ordering the hit list failed: %s", hipGetErrorString(e));
+    } else if (count > have) {  // long list: the rest comes straight from the device
+        e = hipMemcpyAsync(host.p + have * rec_bytes, d_list + have * rec_bytes, (count - have) * rec_bytes, hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess && host_values.p)
+            e = hipMemcpyAsync(host_values.p + have, b.d_values + have, (count - have) * sizeof(float), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess)
+            e = hipStreamSynchronize(st);
+        if (e != hipSuccess)
+            return fail(LM_HIP_ERR_HIP, "fused threshold: read-back failed: %s", hipGetErrorString(e));
+    }
+    out->total = (size_t)count;
+    out->values = host_values.release();
+    if (records)
+        out->set_hits = reinterpret_cast<lm_hip_set_hit *>(host.release());
+    else if (shape.output == Output::Coords)
+        out->coords = reinterpret_cast<lm_hip_coords *>(host.release());
+    else
+        out->hits = reinterpret_cast<lm_hip_hit *>(host.release());
+    return LM_HIP_OK;
+}
+
+// plan, enqueue, deliver.  spec != nullptr: speculative, `count` = the expected records.
+int order_hits(lm_hip_ctx *ctx, const HitList &list, const HitShape &shape, unsigned long long count, const ShortOrder *so,
+               const SegmentCut *cut, HitOutput *out, SpeculativeOrder *spec)
+{
+    static_assert(sizeof(HitRecord) == sizeof(lm_hip_hit), "Output::Records writes records where Output::Hits writes lm_hip_hit");
+    const bool short_on = so && so->on;
+    if ((cut != nullptr) != (shape.output == Output::Records) || (cut && short_on))
+        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the segment pass needs position keys and the long ordering");
+    out->job_start.assign(shape.njobs + 1, 0);
+    out->total = 0;
+    out->ordering = "none/counted";
+    if (!spec && count == 0)
+        return LM_HIP_OK;
+    if (shape.max_low > kLowMask + 1)
+        return fail(LM_HIP_ERR_CAPACITY, "fused threshold: %llu cells per job exceed the 2^40 key space", shape.max_low);
+    Request rq;
+    rq.speculative = spec != nullptr;
+    rq.count = count;
+    rq.cap = list.cap;
+    rq.njobs = shape.njobs;
+    rq.max_low = std::max<unsigned long long>(shape.max_low, 1);
+    rq.output = shape.output;
+    rq.sort_hits = ctx->sort_hits;
+    rq.num_cus = (unsigned)ctx->num_cus;
+    if (short_on)
+        rq.short_geom = *so;
+    rq.seg_waves_per_group = segment_cut_waves(1);
+    rq.staging_cap = kPinHitStaging.cap;
+    rq.readback_cap = kPinHitReadback.cap;
+    const Geometry g = choose_form(rq);
+    if (!g.short_matches || (short_on && list.d_counters != so->counters))
+        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the short ordering was begun with another geometry");
+    size_t sort_temp = 0;
+    if (g.form == Form::Sorted) {  // (the seam of the plan: rocPRIM tells the size of the sort's temporary storage)
+        unsigned long long *kp = nullptr;
+        float *vp = nullptr;
+        LM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_temp, kp, kp, vp, vp, (size_t)g.n_sort, 0u, (unsigned)g.end_bit, ctx->stream));
+    }
+    const Plan p = lay_out(rq, g, sort_temp);
+    static const char *const kNames[2][3] = {{"short/counted", "buckets/counted", "sorted/counted"},
+                                             {"short/speculative", "buckets/speculative", "sorted/speculative"}};
+    out->ordering = kNames[spec ? 1 : 0][(int)p.form];
+    if (spec && !p.staging_fits) {
+        spec->outcome = SpeculativeOrder::TooCoarse;  // too many jobs for the staging block: the caller runs the counted form
+        unsigned long long counts[2];
+        LM_TRY(read_back_counters(ctx, ctx->stream, list.d_counters, counts));
+        spec->hits = counts[0];
+        spec->candidates = counts[1];
+        if (counts[0] > list.cap || counts[1] > list.cand_cap)
+            spec->outcome = SpeculativeOrder::Overflow;
+        return LM_HIP_OK;
+    }
+    LM_TRY(ctx->scratch2.reserve(p.bytes));
+    const Buffers b = carve(ctx, p, spec != nullptr, shape.output);
+    if (spec)
+        memset(b.pin, 0, Plan::p_head_zeroed);  // counters, abort flag and done word (the previous call's results were consumed)
+    LM_TRY(enqueue(ctx, p, b, list, shape, spec != nullptr, so, cut, sort_temp));
+    return deliver(ctx, p, b, list, shape, count, out, spec);
+}
 
 }  // namespace
 
 int short_order_begin(lm_hip_ctx *ctx, unsigned long long expected, size_t njobs, unsigned long long max_low, ShortOrder *so)
 {
-    so->on = false;
-    const unsigned long long sized_for = std::max<unsigned long long>(expected, 4096);
-    if (njobs != 1 || sized_for > kShortRecords || max_low == 0 || max_low > kLowMask + 1)
+    static_cast<ShortGeometry &>(*so) = short_geometry(expected, njobs, max_low);
+    if (!so->on)
         return LM_HIP_OK;
-    bucket_geometry(sized_for, njobs, max_low, &so->shift, &so->nb);
-    if (so->nb > (unsigned long long)kShortBuckets)
-        return LM_HIP_OK;
+    so->on = false;  // until the buffers stand
     if (!ctx->d_short) {
         LM_HIP_TRY(hipMalloc(&ctx->d_short, kShortBytes));
         ctx->short_dirty = false;
@@ -418,7 +683,7 @@ int short_order_begin(lm_hip_ctx *ctx, unsigned long long expected, size_t njobs
     } else if (ctx->short_dirty) {
         LM_HIP_TRY(hipMemsetAsync(ctx->d_short, 0, kShortBytes, ctx->stream));
     }
-    ctx->short_dirty = true;  // until order_hits has seen the clean-up through
+    ctx->short_dirty = true;  // until the ordering has seen the clean-up through
     so->counts = ctx->d_short;
     so->counters = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(ctx->d_short) + kShortOffCounters);
     so->counters_copy = reinterpret_cast<unsigned long long *>(reinterpret_cast<char *>(ctx->d_short) + kShortOffCopy);
@@ -439,376 +704,17 @@ void HitOutput::release()
     total = 0;
 }
 
-// `d_hits`: the records (in ctx->scratch) of `njobs` jobs whose keys' low parts are all below
-// `max_low`; `d_counters` = the two device counters {hits, candidates} the scans bumped.
-//
-// count == ~0 ("speculative"): the host does not know the count yet.  The ordering is
-// enqueued right behind the scans with a bucket geometry sized for `expected` records and
-// every array sized for `cap`; counters, job offsets and the first kPrefix records come
-// back in one pinned copy behind ONE synchronisation -- the usual p = 1e-5 scan then costs
-// one host round trip instead of two.  *status: 0 = done, 1 = a list overflowed (counts in
-// counts_out, nothing produced), 2 = counts fine but the geometry guess was too coarse
-// (the caller runs the exact form).  With a known `count` the geometry is exact.
-// On success `out` owns malloc'ed host arrays in key order and job_start[j] ..
-// job_start[j + 1] delimit job j.  Uses ctx->scratch2; synchronises.
-constexpr unsigned long long kPrefix = 12800;  // x 20 B = 256 KB
-
-int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long long *d_counters,
-               unsigned long long count, unsigned long long cap, unsigned long long cand_cap,
-               unsigned long long expected, size_t njobs, unsigned long long max_low, int emit, size_t cols,
-               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so, const SegmentCut *cut)
+int order_hits_speculative(lm_hip_ctx *ctx, const HitList &list, const HitShape &shape, unsigned long long expected,
+                           const ShortOrder *so, const SegmentCut *cut, HitOutput *out, SpeculativeOrder *result)
 {
-    static_assert(sizeof(HitRecord) == sizeof(lm_hip_hit), "EMIT 2 writes records where EMIT 1 writes lm_hip_hit");
-    if (cut && (emit != 1 || (so && so->on)))
-        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the segment pass needs position keys and the long ordering");
-    const bool speculative = count == ~0ull;
-    *status = 0;
-    out->job_start.assign(njobs + 1, 0);
-    out->total = 0;
-    if (!speculative && count == 0)
-        return LM_HIP_OK;
-    if (max_low == 0)
-        max_low = 1;
-    if (max_low > kLowMask + 1)
-        return fail(LM_HIP_ERR_CAPACITY, "fused threshold: %llu cells per job exceed the 2^40 key space",
-                    max_low);
-    const unsigned long long sized_for = speculative ? std::max<unsigned long long>(expected, 4096) : count;
-    const unsigned long long room = speculative ? cap : count;  // records the arrays must hold
-    int shift = 0;
-    unsigned long long nb = 0;
-    bucket_geometry(sized_for, njobs, max_low, &shift, &nb);
-    const bool short_form = so && so->on;
-    if (short_form && (!speculative || so->shift != shift || so->nb != nb || njobs != 1 || d_counters != so->counters))
-        return fail(LM_HIP_ERR_BAD_ARGS, "fused threshold: the short ordering was begun with another geometry");
-    const unsigned long long nbuckets = nb * njobs;
-    const unsigned long long ntiles = (nbuckets + kScanTile - 1) / kScanTile;
+    *result = SpeculativeOrder{};
+    return order_hits(ctx, list, shape, expected, so, cut, out, result);
+}
 
-    const size_t rec_bytes = emit == 0 ? sizeof(lm_hip_coords) : sizeof(lm_hip_hit);
-    // long lists: radix sort (see the head of this file).  Speculative form: the arrays hold the expected count with a
-    // quarter of headroom; a longer list raises the abort flag and the exact form sorts the true count.
-    const bool sorted = ctx->sort_hits && sized_for >= kSortFrom && njobs < (1ull << 22);
-    const unsigned long long n_sort = !sorted ? 0 : speculative ? std::min(room, sized_for + sized_for / 4 + 4096) : count;
-    int end_bit = 41;
-    while ((1ull << (end_bit - 41)) < njobs)
-        ++end_bit;  // keys are below njobs << 40; one spare bit keeps the all-ones sentinel strictly behind them
-    size_t sort_temp = 0;
-    if (sorted) {
-        unsigned long long *kp = nullptr;
-        float *vp = nullptr;
-        LM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, sort_temp, kp, kp, vp, vp, (size_t)n_sort, 0u, (unsigned)end_bit, ctx->stream));
-    }
-    const size_t off_keys_in = 0, off_keys_out = off_keys_in + align16(n_sort * 8);
-    const size_t off_vals_in = off_keys_out + align16(n_sort * 8), off_vals_out = off_vals_in + align16(n_sort * 4);
-    const size_t off_sort_temp = off_vals_out + align16(n_sort * 4);
-    const size_t off_grouped = 0;
-    const size_t off_counts = off_grouped + align16(room * sizeof(HitRecord));
-    const size_t off_offsets = off_counts + (nbuckets * 4 + 255) / 256 * 256;
-    const size_t off_tiles = off_offsets + align16(nbuckets * 8);
-    const size_t off_total = sorted ? (off_sort_temp + sort_temp + 255) / 256 * 256 : off_tiles + align16(ntiles * 8);
-    // head of the list mirrored into the staging block: the previous call's length with headroom,
-    // bounded so that the staging copy stays a small pinned transfer
-    const unsigned long long pre =
-        speculative ? std::min(room, std::min<unsigned long long>(std::max<unsigned long long>(sized_for, 2048), kPrefix)) : 0;
-    const unsigned long long order_pre = cut ? 0 : pre;  // (with a segment pass the head of ITS output is mirrored)
-    // exact form: starts | records | values contiguous in scratch2 (one read-back copy)
-    const size_t off_starts = off_total + 16;
-    const size_t off_out = off_starts + align16((njobs + 1) * 8);
-    const size_t off_values = off_out + align16(room * rec_bytes);
-    // segment pass (seqset.hip): survivors per wavefront | the jobs' new starts | the compacted (record, position, score) list
-    const unsigned seg_grid = (unsigned)std::max<unsigned long long>(
-        std::min<unsigned long long>((sized_for + 1023) / 1024, (unsigned long long)ctx->num_cus * 4), 1);
-    const size_t off_seg_counts = off_values + align16(room * sizeof(float));
-    const size_t off_seg_starts = off_seg_counts + (cut ? align16(segment_cut_waves(seg_grid) * 4) : 0);
-    const size_t off_seg_out = off_seg_starts + (cut ? align16((njobs + 1) * 8) : 0);
-    const size_t bytes = off_seg_out + (cut ? align16(room * sizeof(lm_hip_set_hit)) : 0);
-    // speculative form: the staging block -- counters | abort flag | starts | head of the list --
-    // lives in the context's pinned host buffer and the kernels write it THERE (posted writes
-    // over PCIe, visible after the stream synchronisation): no copy command, no memset
-    const size_t p_abort = 16, p_done = 24, p_starts = 32;
-    const size_t p_out = p_starts + align16((njobs + 1) * 8);
-    const size_t p_values = p_out + align16(pre * (cut ? sizeof(lm_hip_set_hit) : rec_bytes));
-    const size_t p_bytes = p_values + align16(pre * sizeof(float));
-    char *pin = pinned_at<char>(ctx, kPinHitStaging, 0);  // (the exact form reads back through kPinHitReadback, the same bytes)
-    static_assert(sizeof(size_t) == 8, "job offsets are read back as 64-bit values");
-    const size_t starts_bytes = (njobs + 1) * 8;
-    if (speculative && !pinned_at<char>(ctx, kPinHitStaging, p_bytes)) {
-        *status = 2;  // too many jobs for the staging block: the caller runs the exact form
-        LM_TRY(read_back_counters(ctx, ctx->stream, d_counters, counts_out));
-        if (counts_out[0] > cap || counts_out[1] > cand_cap)
-            *status = 1;
-        return LM_HIP_OK;
-    }
-    LM_TRY(ctx->scratch2.reserve(bytes));
-    char *base = static_cast<char *>(ctx->scratch2.ptr);
-    HitRecord *grouped = reinterpret_cast<HitRecord *>(base + off_grouped);
-    unsigned *counts = reinterpret_cast<unsigned *>(base + off_counts);
-    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(base + off_offsets);
-    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(base + off_tiles);
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(base + off_total);
-    if (short_form) {  // histogram, cursors, offsets and the (zero) tiles of the short form live in the context
-        char *sb = reinterpret_cast<char *>(ctx->d_short);
-        counts = reinterpret_cast<unsigned *>(sb);
-        tiles = reinterpret_cast<unsigned long long *>(sb + kShortOffTiles);
-        offsets = reinterpret_cast<unsigned long long *>(sb + kShortOffOffsets);
-    }
-    unsigned long long *header = reinterpret_cast<unsigned long long *>(pin);
-    unsigned *abort_flag = reinterpret_cast<unsigned *>(pin + p_abort);
-    void *pre_out = pin + p_out;
-    float *pre_values = reinterpret_cast<float *>(pin + p_values);
-    unsigned long long *starts =
-        reinterpret_cast<unsigned long long *>(speculative && !cut ? pin + p_starts : base + off_starts);
-    // with a segment pass the ordering's own starts stay on the device (unused); the starts of the compacted list take their place
-    unsigned long long *seg_starts = reinterpret_cast<unsigned long long *>(speculative ? pin + p_starts : base + off_seg_starts);
-    lm_hip_set_hit *d_set = reinterpret_cast<lm_hip_set_hit *>(base + off_seg_out);
-    void *d_out = base + off_out;
-    float *d_values = reinterpret_cast<float *>(base + off_values);
-    if (speculative)
-        memset(pin, 0, 32);  // counters and abort flag (the previous call's results were consumed)
-    // a guess that is off by orders of magnitude (first call of a context: 4 096 expected, millions
-    // found) leaves hundreds of records per bucket and a quadratic ranking pass (23 ms on the JASPAR
-    // batch): give up early, the exact form costs a fraction of a millisecond
-    const unsigned long long max_bucket = speculative ? 256 : ~0ull;
-
-    hipStream_t st = ctx->stream;
-    // short form, option "poll_done" = 1: the end of the call is polled (hits_rank_emit's last workgroup; the word sits in the
-    // zeroed head of the staging block, the ticket next to the context's counters) instead of waited for on the stream.
-    // 2.6-4.4 us less per call when nothing synchronises behind it -- and ~13 us MORE when the caller follows the call with a
-    // device synchronisation of its own, which then finds the ranking kernel still retiring and pays a full wake-up
-    // (bench.py's protocol does: 0.252 -> 0.265 ms).  Hence off unless asked for (profiles/r06_poll_done_ab.txt).
-    unsigned *done_ticket = nullptr, *done_flag = nullptr;
-    unsigned generation = 0;
-    if (short_form && speculative && ctx->poll_done) {
-        done_ticket = reinterpret_cast<unsigned *>(reinterpret_cast<char *>(ctx->d_short) + kShortOffTicket);
-        done_flag = reinterpret_cast<unsigned *>(pin + p_done);
-        generation = next_generation(ctx->short_generation);
-    }
-    const unsigned grid = (unsigned)std::max<unsigned long long>(
-        std::min<unsigned long long>((sized_for + kBlock - 1) / kBlock, (unsigned long long)ctx->num_cus * 32), 1);
-    if (sorted) {
-        unsigned long long *keys_in = reinterpret_cast<unsigned long long *>(base + off_keys_in);
-        unsigned long long *keys_out = reinterpret_cast<unsigned long long *>(base + off_keys_out);
-        float *vals_in = reinterpret_cast<float *>(base + off_vals_in), *vals_out = reinterpret_cast<float *>(base + off_vals_out);
-        hipLaunchKernelGGL(hits_split, dim3(grid), dim3(kBlock), 0, st, d_hits, d_counters, cap, n_sort, keys_in, vals_in,
-                           speculative ? abort_flag : static_cast<unsigned *>(nullptr));
-        LM_HIP_TRY(hipGetLastError());
-        size_t tb = sort_temp;
-        LM_HIP_TRY(rocprim::radix_sort_pairs(base + off_sort_temp, tb, keys_in, keys_out, vals_in, vals_out, (size_t)n_sort, 0u,
-                                             (unsigned)end_bit, st));
-        if (emit == 0)
-            hipLaunchKernelGGL(hits_sorted_emit<0>, dim3(grid), dim3(kBlock), 0, st, keys_out, vals_out, d_counters, cap, n_sort,
-                               (unsigned long long)cols, static_cast<lm_hip_coords *>(d_out), d_values,
-                               static_cast<lm_hip_hit *>(nullptr), pre_out, pre_values, pre,
-                               speculative ? header : static_cast<unsigned long long *>(nullptr));
-        else if (cut)
-            hipLaunchKernelGGL(hits_sorted_emit<2>, dim3(grid), dim3(kBlock), 0, st, keys_out, vals_out, d_counters, cap, n_sort,
-                               (unsigned long long)cols, static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
-                               static_cast<lm_hip_hit *>(d_out), pre_out, pre_values, order_pre,
-                               speculative ? header : static_cast<unsigned long long *>(nullptr));
-        else
-            hipLaunchKernelGGL(hits_sorted_emit<1>, dim3(grid), dim3(kBlock), 0, st, keys_out, vals_out, d_counters, cap, n_sort,
-                               (unsigned long long)cols, static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
-                               static_cast<lm_hip_hit *>(d_out), pre_out, pre_values, pre,
-                               speculative ? header : static_cast<unsigned long long *>(nullptr));
-        hipLaunchKernelGGL(hits_sorted_starts, dim3((unsigned)((njobs + 1 + 255) / 256)), dim3(256), 0, st, keys_out, d_counters, cap,
-                           n_sort, (unsigned long long)njobs, starts);
-        LM_HIP_TRY(hipGetLastError());
-    } else {
-    const bool inline_starts = njobs <= 1024;  // (one workgroup of hits_rank_emit writes them)
-    unsigned *cursors = short_form ? counts + kShortBuckets : nullptr;
-    const unsigned long long *rank_counters = short_form ? so->counters_copy : d_counters;
-    if (short_form) {  // the re-scoring kernel has counted
-        hipLaunchKernelGGL(hits_short_scatter, dim3(grid), dim3(kBlock), 0, st, d_hits, d_counters, cap, shift, (unsigned)nb,
-                           counts, cursors, offsets, grouped, so->counters_copy);
-    } else {
-        LM_HIP_TRY(hipMemsetAsync(counts, 0, (nbuckets * 4 + 255) / 256 * 256, st));  // whole 256-B units: one fill kernel
-        hipLaunchKernelGGL(hits_bucket_count, dim3(grid), dim3(kBlock), 0, st, d_hits, d_counters, cap, shift, nb,
-                           counts);
-        LM_TRY(launch_scan_u32(ctx, counts, nbuckets, offsets, tiles, total));
-        hipLaunchKernelGGL(hits_bucket_scatter, dim3(grid), dim3(kBlock), 0, st, d_hits, d_counters, cap, shift, nb,
-                           offsets, tiles, counts, grouped);
-    }
-    if (emit == 0)
-        hipLaunchKernelGGL(hits_rank_emit<0>, dim3(grid), dim3(kBlock), 0, st, grouped, rank_counters, cap, shift,
-                           nb, nbuckets, offsets, tiles, (unsigned long long)cols,
-                           static_cast<lm_hip_coords *>(d_out), d_values,
-                           static_cast<lm_hip_hit *>(nullptr), max_bucket, abort_flag, pre_out, pre_values, pre,
-                           (unsigned long long)njobs, inline_starts ? starts : nullptr, inline_starts && speculative ? header : nullptr,
-                           short_form ? counts : nullptr, cursors, short_form ? so->counters : nullptr, done_ticket, done_flag,
-                           generation);
-    else if (cut)
-        hipLaunchKernelGGL(hits_rank_emit<2>, dim3(grid), dim3(kBlock), 0, st, grouped, rank_counters, cap, shift,
-                           nb, nbuckets, offsets, tiles, (unsigned long long)cols,
-                           static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
-                           static_cast<lm_hip_hit *>(d_out), max_bucket, abort_flag, pre_out, pre_values, order_pre,
-                           (unsigned long long)njobs, inline_starts ? starts : nullptr, inline_starts && speculative ? header : nullptr,
-                           static_cast<unsigned *>(nullptr), cursors, static_cast<unsigned long long *>(nullptr), done_ticket, done_flag,
-                           generation);
-    else
-        hipLaunchKernelGGL(hits_rank_emit<1>, dim3(grid), dim3(kBlock), 0, st, grouped, rank_counters, cap, shift,
-                           nb, nbuckets, offsets, tiles, (unsigned long long)cols,
-                           static_cast<lm_hip_coords *>(nullptr), static_cast<float *>(nullptr),
-                           static_cast<lm_hip_hit *>(d_out), max_bucket, abort_flag, pre_out, pre_values, pre,
-                           (unsigned long long)njobs, inline_starts ? starts : nullptr, inline_starts && speculative ? header : nullptr,
-                           short_form ? counts : nullptr, cursors, short_form ? so->counters : nullptr, done_ticket, done_flag,
-                           generation);
-    if (!inline_starts)
-        hipLaunchKernelGGL(hits_job_starts, dim3((unsigned)((njobs + 1 + 255) / 256)), dim3(256), 0, st,
-                           (unsigned long long)njobs, nb, nbuckets, d_counters, cap, offsets, tiles, starts,
-                           speculative ? header : static_cast<unsigned long long *>(nullptr));
-    LM_HIP_TRY(hipGetLastError());
-    }
-
-    if (cut)  // drop the windows that leave their record, make the others record-relative, per-job starts anew (seqset.hip)
-        LM_TRY(launch_segment_cut(st, static_cast<const HitRecord *>(d_out), d_counters, sorted ? n_sort : room, njobs, *cut, seg_grid,
-                                  reinterpret_cast<unsigned *>(base + off_seg_counts), seg_starts, d_set,
-                                  static_cast<lm_hip_set_hit *>(pre_out), pre));
-    scan_timer_mark(ctx, st, 3);  // (time_scan) behind the ordering kernels
-    if (cut) {
-        // the read-back of the compacted list: as below, with the survivors' count = the last of the new starts
-        if (speculative) {
-            LM_HIP_TRY(hipStreamSynchronize(st));
-            counts_out[0] = header[0];
-            counts_out[1] = header[1];
-            if (counts_out[0] > cap || counts_out[1] > cand_cap) {
-                *status = 1;
-                return LM_HIP_OK;
-            }
-            if (*reinterpret_cast<unsigned *>(pin + p_abort)) {
-                *status = 2;
-                return LM_HIP_OK;
-            }
-            if (counts_out[0] == 0)
-                return LM_HIP_OK;
-            memcpy(out->job_start.data(), pin + p_starts, starts_bytes);
-        } else {
-            LM_HIP_TRY(hipMemcpyAsync(out->job_start.data(), seg_starts, starts_bytes, hipMemcpyDeviceToHost, st));
-            LM_HIP_TRY(hipStreamSynchronize(st));
-        }
-        const unsigned long long kept = out->job_start[njobs];
-        if (kept > room)
-            return fail(LM_HIP_ERR_HIP, "fused threshold: the segment pass reports %llu of %llu hits", kept, room);
-        if (kept == 0)
-            return LM_HIP_OK;
-        lm_hip_set_hit *host = static_cast<lm_hip_set_hit *>(result_alloc(kept * sizeof(lm_hip_set_hit)));
-        if (!host)
-            return fail(LM_HIP_ERR_OOM, "fused threshold: cannot allocate %llu hits on the host", kept);
-        const unsigned long long have = speculative ? std::min(kept, pre) : 0;
-        memcpy(host, pin + p_out, have * sizeof(lm_hip_set_hit));
-        if (kept > have) {  // long list: the rest comes straight from the device
-            hipError_t e = hipMemcpyAsync(host + have, d_set + have, (kept - have) * sizeof(lm_hip_set_hit), hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess)
-                e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                result_free(host);
-                return fail(LM_HIP_ERR_HIP, "fused threshold: read-back failed: %s", hipGetErrorString(e));
-            }
-        }
-        out->total = (size_t)kept;
-        out->set_hits = host;
-        return LM_HIP_OK;
-    }
-    if (speculative) {
-        // the ranking kernel's last workgroup raises the word behind everything it and the others wrote
-        const bool seen = done_flag && poll_generation(done_flag, generation, 1u << 23);  // bounded: a kernel that never gets there is caught below
-        if (!seen || ctx->scan_timed)  // (option "time_scan": the events behind the kernels are read next -- they must have completed)
-            LM_HIP_TRY(hipStreamSynchronize(st));
-        if (short_form)
-            ctx->short_dirty = false;  // both kernels ran: counts and cursors are zero again
-        counts_out[0] = header[0];
-        counts_out[1] = header[1];
-        if (counts_out[0] > cap || counts_out[1] > cand_cap) {
-            *status = 1;
-            return LM_HIP_OK;
-        }
-        if (*reinterpret_cast<unsigned *>(pin + p_abort)) {
-            *status = 2;
-            return LM_HIP_OK;
-        }
-        count = counts_out[0];
-        if (count == 0)
-            return LM_HIP_OK;
-        void *host = result_alloc(count * rec_bytes);
-        float *host_values = emit == 0 ? static_cast<float *>(result_alloc(count * sizeof(float))) : nullptr;
-        if (!host || (emit == 0 && !host_values)) {
-            result_free(host);
-            result_free(host_values);
-            return fail(LM_HIP_ERR_OOM, "fused threshold: cannot allocate %llu hits on the host", count);
-        }
-        memcpy(out->job_start.data(), pin + p_starts, starts_bytes);
-        const unsigned long long have = std::min(count, pre);
-        memcpy(host, pin + p_out, have * rec_bytes);
-        if (host_values)
-            memcpy(host_values, pin + p_values, have * sizeof(float));
-        if (count > have) {  // long list: the rest comes straight from the device
-            hipError_t e = hipMemcpyAsync(static_cast<char *>(host) + have * rec_bytes,
-                                          static_cast<char *>(d_out) + have * rec_bytes,
-                                          (count - have) * rec_bytes, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess && host_values)
-                e = hipMemcpyAsync(host_values + have, d_values + have, (count - have) * sizeof(float),
-                                   hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess)
-                e = hipStreamSynchronize(st);
-            if (e != hipSuccess) {
-                result_free(host);
-                result_free(host_values);
-                return fail(LM_HIP_ERR_HIP, "fused threshold: read-back failed: %s", hipGetErrorString(e));
-            }
-        }
-        out->total = (size_t)count;
-        if (emit == 0) {
-            out->coords = static_cast<lm_hip_coords *>(host);
-            out->values = host_values;
-        } else {
-            out->hits = static_cast<lm_hip_hit *>(host);
-        }
-        return LM_HIP_OK;
-    }
-
-    void *host = result_alloc(count * rec_bytes);
-    float *host_values = emit == 0 ? static_cast<float *>(result_alloc(count * sizeof(float))) : nullptr;
-    if (!host || (emit == 0 && !host_values)) {
-        result_free(host);
-        result_free(host_values);
-        return fail(LM_HIP_ERR_OOM, "fused threshold: cannot allocate %llu hits on the host", count);
-    }
-    // Read-back.  starts | records | values are contiguous in scratch2: small results come back
-    // as ONE copy into the pinned buffer (a copy into pageable memory costs ~15 us each),
-    // large ones go straight into the arrays handed to the caller.
-    const size_t block_bytes = off_values + count * sizeof(float) - off_starts;
-    hipError_t e;
-    if (pinned_at<char>(ctx, kPinHitReadback, block_bytes)) {
-        e = hipMemcpyAsync(pin, base + off_starts, block_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-        if (e == hipSuccess) {
-            memcpy(out->job_start.data(), pin, starts_bytes);
-            memcpy(host, pin + (off_out - off_starts), count * rec_bytes);
-            if (host_values)
-                memcpy(host_values, pin + (off_values - off_starts), count * sizeof(float));
-        }
-    } else {
-        e = hipMemcpyAsync(out->job_start.data(), starts, starts_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(host, d_out, count * rec_bytes, hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess && host_values)
-            e = hipMemcpyAsync(host_values, d_values, count * sizeof(float), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess)
-            e = hipStreamSynchronize(st);
-    }
-    if (e != hipSuccess) {
-        result_free(host);
-        result_free(host_values);
-        return fail(LM_HIP_ERR_HIP, "fused threshold: ordering the hit list failed: %s",
-                    hipGetErrorString(e));
-    }
-    out->total = (size_t)count;
-    if (emit == 0) {
-        out->coords = static_cast<lm_hip_coords *>(host);
-        out->values = host_values;
-    } else {
-        out->hits = static_cast<lm_hip_hit *>(host);
-    }
-    return LM_HIP_OK;
+int order_hits_counted(lm_hip_ctx *ctx, const HitList &list, const HitShape &shape, unsigned long long count,
+                       const SegmentCut *cut, HitOutput *out)
+{
+    return order_hits(ctx, list, shape, count, nullptr, cut, out, nullptr);
 }
 
 }  // namespace lm

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "lightmotif_hip.h"
+#include "hits_plan.hpp"
 
 namespace lm {
 
@@ -149,6 +150,22 @@ static_assert(kPinListHead.end() <= kPinUploadHead.off && kPinU8Out.end() <= kPi
 // more than half of the scans it follows).
 void *result_alloc(size_t bytes);
 void result_free(void *p);  // what lm_hip_free does: back to the pool, or free()
+// `n` T from result_alloc, owned until released to the caller: whatever returns early frees them
+template <class T>
+struct ResultArray {
+    T *p = nullptr;
+    ResultArray() = default;
+    explicit ResultArray(size_t n) : p(static_cast<T *>(result_alloc(n * sizeof(T)))) {}
+    ResultArray(const ResultArray &) = delete;
+    ResultArray &operator=(const ResultArray &) = delete;
+    ~ResultArray() { result_free(p); }
+    T *release()
+    {
+        T *r = p;
+        p = nullptr;
+        return r;
+    }
+};
 
 }  // namespace lm
 
@@ -542,6 +559,7 @@ struct HitOutput {
     float *values = nullptr;
     lm_hip_hit *hits = nullptr;       // HitKeys::Position: (sequence position, score)
     lm_hip_set_hit *set_hits = nullptr;  // ... with a SegmentCut: (record, position in the record, score)
+    const char *ordering = "none";    // diagnostics (LM_HIP_TRACE): "<form>/speculative" or "<form>/counted", hits.hip
     void release();
 };
 
@@ -574,23 +592,44 @@ int launch_score_argmax_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n,
 struct HitRecord;
 // Short lists of ONE job (a scan at p = 1e-5 leaves ~10^4 hits per Gbp): the re-scoring kernel counts the records per
 // bucket as it stores them, so the ordering behind it is two launches instead of five (hits.hip).  `on` = the geometry
-// below was handed to launch_rescore and order_hits must be called with the same object.
-struct ShortOrder {
-    bool on = false;
-    int shift = 0;
-    unsigned long long nb = 0;
+// below was handed to launch_rescore and order_hits_speculative must be called with the same object.
+struct ShortOrder : hits::ShortGeometry {
     unsigned *counts = nullptr;
     // the list's two counters {hits, candidates} live in the context as well, zero between calls: the scans need no
     // head block copied in first (the single job reaches the re-scoring kernel as an argument)
     unsigned long long *counters = nullptr, *counters_copy = nullptr;
 };
 int short_order_begin(lm_hip_ctx *ctx, unsigned long long expected, size_t njobs, unsigned long long max_low, ShortOrder *so);
-// count == ~0: speculative (the host has not read the counters yet); see hits.hip
-int order_hits(lm_hip_ctx *ctx, const HitRecord *d_hits, const unsigned long long *d_counters,
-               unsigned long long count, unsigned long long cap, unsigned long long cand_cap,
-               unsigned long long expected, size_t njobs, unsigned long long max_low, int emit, size_t cols,
-               HitOutput *out, int *status, unsigned long long counts_out[2], const ShortOrder *so = nullptr,
-               const SegmentCut *cut = nullptr);
+// The list to order: `d_hits` (in ctx->scratch) holds the records, `d_counters` the two device counters {hits,
+// candidates} the scans bumped, `cap` / `cand_cap` the capacities those were bumped against.
+struct HitList {
+    const HitRecord *d_hits;
+    const unsigned long long *d_counters;
+    unsigned long long cap, cand_cap;
+};
+// `njobs` jobs whose keys' low parts are all below `max_low`; `cols` turns a low part into hits::Output::Coords.
+// hits::Output::Records goes with a SegmentCut (and never with a ShortOrder): out->set_hits is the result.
+struct HitShape {
+    size_t njobs;
+    unsigned long long max_low;
+    hits::Output output;
+    size_t cols;
+};
+// What became of a speculative ordering.  Overflow: a list outgrew its capacity, nothing was produced (grow by `hits` /
+// `candidates` and scan again).  TooCoarse: the counts are fine but the geometry guessed from `expected` was not (or the
+// batch has too many jobs for the staging block): order_hits_counted does it with hits known.
+struct SpeculativeOrder {
+    enum { Done, Overflow, TooCoarse } outcome = Done;
+    unsigned long long hits = 0, candidates = 0;
+};
+// Speculative: the host has not read the counters; the ordering is enqueued behind the scans, sized for `expected`
+// records, and the counts come back with the list behind ONE synchronisation.  Counted: `count` (<= cap) records are
+// there; nothing to report but the list.  On success `out` owns host arrays in key order, job j = [job_start[j],
+// job_start[j + 1]), and out->ordering names the form.  Both use ctx->scratch2 and synchronise.
+int order_hits_speculative(lm_hip_ctx *ctx, const HitList &list, const HitShape &shape, unsigned long long expected,
+                           const ShortOrder *so, const SegmentCut *cut, HitOutput *out, SpeculativeOrder *result);
+int order_hits_counted(lm_hip_ctx *ctx, const HitList &list, const HitShape &shape, unsigned long long count,
+                       const SegmentCut *cut, HitOutput *out);
 // seqset.hip: the two launches of the segment pass over `ordered` (records with their full keys, in key order; the
 // count is read from the device).  `grid` workgroups; wave_counts needs segment_cut_waves(grid) entries.
 unsigned segment_cut_waves(unsigned grid);
@@ -604,6 +643,55 @@ constexpr int kScanTile = 1024;
 int launch_scan_u32(lm_hip_ctx *ctx, const unsigned *counts, unsigned long long n,
                     unsigned long long *offsets, unsigned long long *tiles,
                     unsigned long long *total);
+static_assert(kScanTile == hits::kPlanScanTile, "hits_plan.hpp lays out the scan's arrays");
+// its four arrays for n counts, carved from `base` (hits::scan_layout(n).bytes of it, 16-byte aligned)
+struct ScanArrays {
+    unsigned *counts;
+    unsigned long long *offsets, *tiles, *total;
+};
+inline ScanArrays carve_scan_u32(void *base, unsigned long long n)
+{
+    const hits::ScanLayout s = hits::scan_layout(n);
+    char *b = static_cast<char *>(base);
+    return {reinterpret_cast<unsigned *>(b + s.off_counts), reinterpret_cast<unsigned long long *>(b + s.off_offsets),
+            reinterpret_cast<unsigned long long *>(b + s.off_tiles), reinterpret_cast<unsigned long long *>(b + s.off_total)};
+}
+inline int launch_scan_u32(lm_hip_ctx *ctx, const ScanArrays &a, unsigned long long n)
+{
+    return launch_scan_u32(ctx, a.counts, n, a.offsets, a.tiles, a.total);
+}
+// Threshold over a materialised matrix cut into `nchunks` chunks (reduce.hip: f32, discrete.hip: u8): `count(counts)`
+// launches the kernel that leaves the hits per chunk, `fill(arrays, d_out)` the one that writes their coordinates in
+// row-major order; synchronises.  *coords: from result_alloc, or null when nothing passed.
+template <class Count, class Fill>
+int threshold_by_chunks(lm_hip_ctx *ctx, const char *what, unsigned long long nchunks, Count count, Fill fill,
+                        lm_hip_coords **coords, size_t *n)
+{
+    LM_TRY(ctx->scratch.reserve(hits::scan_layout(nchunks).bytes));
+    const ScanArrays a = carve_scan_u32(ctx->scratch.ptr, nchunks);
+    count(a.counts);
+    LM_TRY(launch_scan_u32(ctx, a, nchunks));
+    unsigned long long total = 0;
+    LM_TRY(read_back(ctx, ctx->stream, a.total, &total));
+    if (total == 0)
+        return LM_HIP_OK;
+    ResultArray<lm_hip_coords> host((size_t)total);
+    if (!host.p)
+        return fail(LM_HIP_ERR_OOM, "%s: cannot allocate %llu hits on the host", what, total);
+    LM_TRY(ctx->scratch2.reserve(total * sizeof(lm_hip_coords)));
+    lm_hip_coords *d_out = static_cast<lm_hip_coords *>(ctx->scratch2.ptr);
+    fill(a, d_out);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess)
+        e = hipMemcpyAsync(host.p, d_out, total * sizeof(lm_hip_coords), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess)
+        e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess)
+        return fail(LM_HIP_ERR_HIP, "%s fill failed: %s", what, hipGetErrorString(e));
+    *coords = host.release();
+    *n = (size_t)total;
+    return LM_HIP_OK;
+}
 
 int launch_argmax(lm_hip_ctx *ctx, const float *d_scores, size_t rows, size_t stride,
                   size_t cols, int first_cell_rule, ArgmaxRecord *out);

@@ -405,53 +405,19 @@ int launch_threshold(lm_hip_ctx *ctx, const float *d_scores, size_t rows, size_t
     if (ncells == 0)
         return LM_HIP_OK;
     const unsigned long long nchunks = (ncells + kChunk - 1) / kChunk;
-    const unsigned long long ntiles = (nchunks + kScanTile - 1) / kScanTile;
     const int flat = stride == cols && (reinterpret_cast<uintptr_t>(d_scores) % 16 == 0);
-    // scratch: counts u32[nchunks] | offsets u64[nchunks] | tile totals u64[ntiles] | total u64
-    const size_t off_counts = 0;
-    const size_t off_offsets = (nchunks * 4 + 15) / 16 * 16;
-    const size_t off_tiles = off_offsets + nchunks * 8;
-    const size_t off_total = off_tiles + ntiles * 8;
-    LM_TRY(ctx->scratch.reserve(off_total + 16));
-    char *base = static_cast<char *>(ctx->scratch.ptr);
-    unsigned *counts = reinterpret_cast<unsigned *>(base + off_counts);
-    unsigned long long *offsets = reinterpret_cast<unsigned long long *>(base + off_offsets);
-    unsigned long long *tiles = reinterpret_cast<unsigned long long *>(base + off_tiles);
-    unsigned long long *total = reinterpret_cast<unsigned long long *>(base + off_total);
-
-    hipLaunchKernelGGL(threshold_count, dim3((unsigned)nchunks), dim3(kBlock), 0, ctx->stream,
-                       d_scores, ncells, (unsigned long long)stride, (unsigned)cols, flat, t, counts);
-    LM_TRY(launch_scan_u32(ctx, counts, nchunks, offsets, tiles, total));
-    unsigned long long count = 0;
-    LM_TRY(read_back(ctx, ctx->stream, total, &count));
-    if (count == 0)
-        return LM_HIP_OK;
-
-    lm_hip_coords *host = static_cast<lm_hip_coords *>(result_alloc(count * sizeof(lm_hip_coords)));
-    if (!host)
-        return fail(LM_HIP_ERR_OOM, "threshold: cannot allocate %llu hits on the host", count);
-    int st = ctx->scratch2.reserve(count * sizeof(lm_hip_coords));
-    if (st != LM_HIP_OK) {
-        result_free(host);
-        return st;
-    }
-    lm_hip_coords *d_out = static_cast<lm_hip_coords *>(ctx->scratch2.ptr);
-    hipLaunchKernelGGL(threshold_fill, dim3((unsigned)((nchunks + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, ctx->stream, d_scores, ncells, (unsigned long long)stride,
-                       (unsigned)cols, flat, t, counts, nchunks, offsets, tiles, d_out);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(host, d_out, count * sizeof(lm_hip_coords), hipMemcpyDeviceToHost,
-                           ctx->stream);
-    if (e == hipSuccess)
-        e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        result_free(host);
-        return fail(LM_HIP_ERR_HIP, "threshold fill failed: %s", hipGetErrorString(e));
-    }
-    *coords = host;
-    *n = (size_t)count;
-    return LM_HIP_OK;
+    return threshold_by_chunks(
+        ctx, "threshold", nchunks,
+        [&](unsigned *counts) {
+            hipLaunchKernelGGL(threshold_count, dim3((unsigned)nchunks), dim3(kBlock), 0, ctx->stream,
+                               d_scores, ncells, (unsigned long long)stride, (unsigned)cols, flat, t, counts);
+        },
+        [&](const ScanArrays &a, lm_hip_coords *d_out) {
+            hipLaunchKernelGGL(threshold_fill, dim3((unsigned)((nchunks + kBlock - 1) / kBlock)),
+                               dim3(kBlock), 0, ctx->stream, d_scores, ncells, (unsigned long long)stride,
+                               (unsigned)cols, flat, t, a.counts, nchunks, a.offsets, a.tiles, d_out);
+        },
+        coords, n);
 }
 
 }  // namespace lm

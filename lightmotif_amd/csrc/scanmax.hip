@@ -400,10 +400,8 @@ static int scan_max_by_list(lm_hip_ctx *ctx, const lm_hip_pssm *pssm, const lm_h
             sorted.emplace_back(h_recs[i].key, h_recs[i].value);
         std::sort(sorted.begin(), sorted.end(), [](const auto &a, const auto &b) { return a.first < b.first; });  // (cells are unique)
     } else {
-        int status = 0;
-        unsigned long long counts[2];
-        LM_TRY(order_hits(ctx, fo.hits, fo.hit_count, count, cap, ccap, count, 1, ((unsigned long long)rows * cols) << 8, 1, cols, &out,
-                          &status, counts));
+        LM_TRY(order_hits_counted(ctx, HitList{fo.hits, fo.hit_count, cap, ccap},
+                                  HitShape{1, ((unsigned long long)rows * cols) << 8, hits::Output::Hits, cols}, count, nullptr, &out));
     }
     // the walk (scan.rs:229-242), over records in row-major cell order
     const unsigned long long total = (unsigned long long)rows * cols;

@@ -255,62 +255,44 @@ static int launch_threshold_scans(lm_hip_ctx *ctx, const ScoreArgs *jobs, const 
 struct ListSizes {
     unsigned long long cap, ccap, count, ncand;
     bool ordered;  // the speculative ordering held: one synchronisation
+    bool again;    // a list overflowed and its capacity has grown: scan again
 };
 
-// the tail of an attempt: counts and ordered list; *again: a list overflowed, its capacity in `ls` has grown: scan again
-static int order_or_grow(lm_hip_ctx *ctx, bool speculate, const FusedOut &fo, const char *base, const ShortOrder &so,
-                         const SegmentCut *segp, unsigned long long expected, size_t n, unsigned long long max_low, int emit,
-                         size_t cols, HitOutput *out, ListSizes *ls, bool *again)
+// the tail of an attempt: counts and ordered list, or ls->again
+static int order_or_grow(lm_hip_ctx *ctx, bool speculate, const FusedOut &fo, const ShortOrder &so, const SegmentCut *segp,
+                         const HitShape &shape, unsigned long long expected, HitOutput *out, ListSizes *ls)
 {
-    unsigned long long &cap = ls->cap, &ccap = ls->ccap, &count = ls->count, &ncand = ls->ncand;
-    *again = true;
+    ls->again = true;
     if (speculate) {
         // First try: enqueue the ordering right behind the scans, sized from the previous
         // call's count, and learn the counts from the same single synchronisation.
-        int status = 0;
-        unsigned long long counts[2] = {0, 0};
-        LM_TRY(order_hits(ctx, fo.hits, fo.hit_count, ~0ull, cap, ccap, expected, n, max_low, emit, cols, out,
-                          &status, counts, &so, segp));
-        count = counts[0];
-        ncand = counts[1];
-        ls->ordered = status == 0;
-        if (status == 1) {  // a list overflowed: grow and run the scans again
-            ctx->last_cand_count = ncand;
-            if (ncand > ccap) {
-                ccap = ncand + ncand / 8 + 64;
-                return LM_HIP_OK;
-            }
-            ctx->last_hit_count = count;
-            cap = count + count / 8 + 64;
-            return LM_HIP_OK;
-        }
+        SpeculativeOrder spec;
+        LM_TRY(order_hits_speculative(ctx, HitList{fo.hits, fo.hit_count, ls->cap, ls->ccap}, shape, expected, &so, segp, out, &spec));
+        ls->count = spec.hits;
+        ls->ncand = spec.candidates;
+        ls->ordered = spec.outcome == SpeculativeOrder::Done;
     } else {
         unsigned long long counts[2];
-        LM_TRY(read_back_counters(ctx, ctx->stream, base, counts));
-        count = counts[0];
-        ncand = counts[1];
-        if (ncand > ccap) {
-            // the hit count of a truncated candidate list means nothing yet
-            ctx->last_cand_count = ncand;
-            ccap = ncand + ncand / 8 + 64;
-            return LM_HIP_OK;
-        }
-        if (count > cap) {
-            ctx->last_hit_count = count;
-            cap = count + count / 8 + 64;
-            return LM_HIP_OK;
-        }
+        LM_TRY(read_back_counters(ctx, ctx->stream, fo.hit_count, counts));
+        ls->count = counts[0];
+        ls->ncand = counts[1];
     }
-    *again = false;
-    ctx->last_cand_count = ncand;
-    ctx->last_hit_count = count;
-    if (!ls->ordered) {  // exact form: the count is known
-        int status = 0;
-        unsigned long long counts[2];
-        // (after a short form that gave up, the list's counters have been cleared: their copy still holds them)
-        LM_TRY(order_hits(ctx, fo.hits, so.on ? so.counters_copy : fo.hit_count, count, cap, ccap, count, n, max_low, emit, cols,
-                          out, &status, counts, nullptr, segp));
+    // a list overflowed: grow and run the scans again (the hit count of a truncated candidate list means nothing yet)
+    if (ls->ncand > ls->ccap) {
+        ctx->last_cand_count = ls->ncand;
+        ls->ccap = ls->ncand + ls->ncand / 8 + 64;
+        return LM_HIP_OK;
     }
+    if (speculate || ls->count <= ls->cap)  // (as ever: a counted attempt whose hit list overflowed leaves the candidates' figure alone)
+        ctx->last_cand_count = ls->ncand;
+    ctx->last_hit_count = ls->count;
+    if (ls->count > ls->cap) {
+        ls->cap = ls->count + ls->count / 8 + 64;
+        return LM_HIP_OK;
+    }
+    ls->again = false;
+    if (!ls->ordered)  // the count is known (after a short form that gave up, the list's counters have been cleared: their copy still holds them)
+        LM_TRY(order_hits_counted(ctx, HitList{fo.hits, so.on ? so.counters_copy : fo.hit_count, ls->cap, ls->ccap}, shape, ls->count, segp, out));
     return LM_HIP_OK;
 }
 
@@ -439,10 +421,10 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
             seg.job_m_stride = sizeof(RescoreJob);
         }
         const auto t_scan = std::chrono::steady_clock::now();
-        bool again = false;
-        LM_TRY(order_or_grow(ctx, attempt == 0 && ctx->speculate_order, fo, base, so, cut ? &seg : nullptr, expected, n, max_low,
-                             keys == HitKeys::Position ? 1 : 0, jobs[0].cols, out, &ls, &again));
-        if (again)
+        const HitShape shape{n, max_low, cut ? hits::Output::Records : keys == HitKeys::Position ? hits::Output::Hits : hits::Output::Coords,
+                             jobs[0].cols};
+        LM_TRY(order_or_grow(ctx, attempt == 0 && ctx->speculate_order, fo, so, cut ? &seg : nullptr, shape, expected, out, &ls));
+        if (ls.again)
             continue;
         scan_timer_read(ctx);
         if (ctx->last_phase_ms[0] >= 0)  // (time_scan) the host's share: everything of the call the events do not cover
@@ -450,9 +432,9 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
                                     (ctx->last_phase_ms[0] + std::max(ctx->last_phase_ms[1], 0.0f) + std::max(ctx->last_phase_ms[2], 0.0f));
         if (getenv("LM_HIP_TRACE")) {
             const auto t_end = std::chrono::steady_clock::now();
-            fprintf(stderr, "[lm_hip] fused threshold: %zu jobs, %llu candidates, %llu hits; %s; scans enqueued in "
+            fprintf(stderr, "[lm_hip] fused threshold: %zu jobs, %llu candidates, %llu hits; %s [%s]; scans enqueued in "
                             "%.3f ms, wait + ordering + read-back %.3f ms\n", n, ls.ncand, ls.count,
-                    ls.ordered ? "ordered behind the scans (one synchronisation)" : "ordered after reading the count",
+                    ls.ordered ? "ordered behind the scans (one synchronisation)" : "ordered after reading the count", out->ordering,
                     std::chrono::duration<double, std::milli>(t_scan - t_begin).count(),
                     std::chrono::duration<double, std::milli>(t_end - t_scan).count());
         }
