@@ -35,6 +35,29 @@
  *    stream; results that come back to the host (argmax, threshold, counts)
  *    synchronise that stream before returning.  Host-pointer functions are
  *    fully synchronous (the GPU analogue of the `_mm_sfence` at avx2.rs:198);
+ *  - pointers, strides and alignment of the `*_dptr` functions and of lm_hip_seq_adopt_dptr: a device pointer needs
+ *    the alignment of its ELEMENT only (f32 matrices: 4 bytes; u8 matrices, ASCII and symbol bytes: none), and every
+ *    stride >= cols is accepted, whatever cols is -- a torch view with a storage offset, one row shard of a wider
+ *    buffer, a matrix whose rows are wider than their live columns.  `seq_stride`, `out_stride` and `stride` are
+ *    independent of each other.  The results, and the cells written, are the same at every placement: the bytes
+ *    between `cols` and the stride of a row are never read, and never written except by Stripe / configure_wrap, which
+ *    say so below.  No placement is refused; what depends on it is the KERNEL, hence the speed (lm_hip_ctx_last_kernel
+ *    and lm_hip_ctx_launch_tally tell which one ran; tests/test_gpu_foreign_geometry.py holds the library to this list):
+ *      . Score<f32> (store and fused forms): the unrolled kernels (score_c32<M,MODE>, the prefilter scans) need
+ *        cols == 32 (the plain store: also 16) and seq_stride == 32, a store also out_stride == cols.  Otherwise a store
+ *        runs the LDS-tiled kernel (score_tiled) or goes cell by cell, a fused form goes cell by cell
+ *        (score_generic<1>, <2>).  The output pointer needs no more than its 4 bytes.
+ *      . d_seq % 4 != 0 (natural strides): no kernel with dword symbol loads.  Stores of M <= 36 run the byte-load
+ *        member of the family, longer motifs (the long and very long families, slices) the tiled kernel; fused forms
+ *        scan one symbol per lookup with byte loads (no pair scan, no 4-row symbol blocks, no multi-motif pass) and
+ *        go cell by cell beyond M = 36; Score<u8> looks one symbol up at a time; lm_hip_scan_max_f32 walks
+ *        materialised windows.
+ *      . Score<u8>: as Score<f32>, and d_out % 4 != 0 goes cell by cell (score_generic_u8).
+ *      . Maximum / Threshold (f32 and u8): stride == cols with a 16-byte aligned pointer is read as one flat array,
+ *        16 bytes per lane; anything else cell by cell.
+ *      . Encode: 16 bytes per lane when source and destination are both 16-byte aligned, else byte by byte.
+ *      . Stripe: cols == 32, stride == 32 and d_data % 16 == 0 stores 16 bytes per lane; d_data % 4 == 0 with
+ *        stride % 4 == 0 stores dwords; anything else bytes.  configure_wrap is byte-wise throughout.
  *  - all entry points are thread-safe; a context serialises its own calls.
  */
 #ifndef LIGHTMOTIF_HIP_H
