@@ -522,6 +522,43 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
 int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set,
                             lm_hip_set_best *best);
 
+/* How many windows of every motif reach a cut-off in every record of the set, at up to LM_HIP_MAX_COUNT_LEVELS cut-offs
+ * per motif, in ONE call and without a hit list: the count the reference's CLI would reach by collecting the hits of
+ * every (motif, record) job (main.rs:502-561) and counting them per record.
+ *   thresholds   thresholds[i * levels + l] is cut-off l of motif i, 1 <= levels <= LM_HIP_MAX_COUNT_LEVELS; several
+ *                cut-offs of one motif cost one walk over the set
+ *   counts       counts[(i * levels + l) * records + r], the caller's memory (n * levels * records cells); every cell is
+ *                written, zeros included
+ * A cell holds the number of positions p = 0 .. L_r - M of record r (all inside the record: scan.rs:185-190, per RECORD)
+ * whose window score v satisfies v >= t under f32 comparison, v being the score score_into gives: M sequential f32 adds
+ * from +0.0 in row order (pli/mod.rs:96-105), bit for bit the score of the record striped alone.  NaN windows are never
+ * counted, -inf windows only when t is -inf, a NaN threshold counts nothing; windows that straddle two records or reach
+ * the padding are never counted.  For every threshold value a cell equals the number of entries with that record in
+ * lm_hip_scan_threshold_seqset's list for motif i at t.  A motif with no window anywhere (no rows, or longer than the
+ * sequence) gives zeros.
+ * Deterministic, identical from call to call and with the prefilter on or off: the route is exact f32 throughout and its
+ * merge is a sum of integers (csrc/seqset_count.hip: the walk of lm_hip_scan_best_seqset with per-lane counters that
+ * reach the cells through 32-bit atomic adds; lm_hip_ctx_last_kernel names `seqset_count_fused<M>` up to M = 36,
+ * `seqset_count_generic` beyond).
+ * Measured on one MI355X (tools/seqset_bench.py --count, profiles/seqset_count_bench.json; 2 000 records x 500 bp x 8
+ * JASPAR motifs, the set resident, medians of 15 alternating runs), against lm_hip_scan_threshold_seqset at the same
+ * thresholds plus one count per motif on the host, the cheapest way before: 0.135 ms against 2.14 ms at p = 1e-1 (768 000
+ * hits, 15.8 x), 0.118 against 0.345 ms at 1e-2 (2.9 x), 0.111 against 0.162 ms at 1e-3 (1.5 x); at 1e-4 and 1e-5 the two
+ * are level within the spread between runs (list / count = 1.18 and 1.18 in one run, 1.04 and 0.96 in its repeat), so the
+ * crossover lies at about p = 1e-5 and from there down the list route, which also says WHERE the hits are, stays the
+ * right call.  Three cut-offs (1e-1, 1e-2, 1e-3) in one call: 0.143 ms against 4.19 ms for the list at 1e-1 plus three
+ * counts (29 x).  The same call of lm_hip_scan_best_seqset, the same walk, takes 0.131-0.135 ms: counting costs 0.83-1.0 x
+ * the best hit (4-byte cells, no finalize kernel).
+ * LM_HIP_ERR_WRAP when the set's wrap < max(M) - 1; LM_HIP_ERR_BAD_ARGS, before any launch, on null arguments (with
+ * n > 0 a null `thresholds`, and a null `counts` when the set has records), `levels` of 0 or above
+ * LM_HIP_MAX_COUNT_LEVELS, or a matrix whose alphabet size differs from the set's; LM_HIP_OK with nothing written when
+ * n == 0 or the set has no records; LM_HIP_ERR_CAPACITY, before any launch, when a record holds 2^32 or more symbols (a
+ * cell is 32 bits); LM_HIP_ERR_OOM when the device cannot hold the cells of one motif (motifs are scanned in groups that
+ * bound the block at 256 MB). */
+#define LM_HIP_MAX_COUNT_LEVELS 4
+int lm_hip_scan_count_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds,
+                             size_t levels, size_t n, const lm_hip_seqset *set, uint32_t *counts);
+
 /* SymbolCount::count_symbols of a StripedSequence (seq.rs:444-483, the loop of seq.rs:466-482), and the same for every
  * record of a set in ONE call: what Background::from_sequence / from_sequences (abc.rs:404-456) count before
  * Background::from_counts (abc.rs:389-402) turns the table into frequencies, on the resident bytes (csrc/composition.hip).

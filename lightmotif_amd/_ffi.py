@@ -37,6 +37,7 @@ class RegistryRow(C.Structure):
 
 # lm_hip_registry_row::family (LM_HIP_FAMILY_*) and the slots of the c32 family, in the header's order
 FAMILIES = ("c32", "pre", "preblk", "pre2", "pre2_protein", "pre2_multi", "u8", "u8_pairs", "best_fused")
+MAX_COUNT_LEVELS = 4   # LM_HIP_MAX_COUNT_LEVELS: cut-offs per motif of lm_hip_scan_count_seqset
 SLOTS = ("STORE", "ARGMAX", "THRESHOLD", "STORE_QL", "STORE_ARGMAX", "CONTINUE", "STORE_C16", "STORE_TRACK")
 
 
@@ -126,6 +127,7 @@ SIGNATURES = {
     "lm_hip_seqset_destroy": (C.c_int, [_vp]),
     "lm_hip_scan_threshold_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _szp, C.POINTER(C.POINTER(SetHit))]),
     "lm_hip_scan_best_seqset": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, C.POINTER(SetBest)]),
+    "lm_hip_scan_count_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _sz, _vp, C.POINTER(C.c_uint32)]),
     "lm_hip_seq_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_windows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),

@@ -1648,6 +1648,30 @@ public:
             }
         return out;
     }
+    // How many windows of every motif reach its cut-offs in every record of a set in one call, without a hit list
+    // (lm_hip_scan_count_seqset): thresholds[i * levels + l] is cut-off l of motif i, 1 <= levels <=
+    // LM_HIP_MAX_COUNT_LEVELS; out[i][l][r] counts the windows position + M <= len(record) (scan.rs:185-190) of record r
+    // with score >= that cut-off in f32.  NaN windows and NaN thresholds count nothing.
+    std::vector<std::vector<std::vector<uint32_t>>> scan_count(const std::vector<const ScoringMatrix<A> *> &pssms,
+                                                               const std::vector<float> &thresholds, size_t levels,
+                                                               const SequenceSet<A> &set) const
+    {
+        const size_t n = pssms.size(), records = set.records();
+        if (levels < 1 || levels > (size_t)LM_HIP_MAX_COUNT_LEVELS)
+            throw std::invalid_argument("1 ... LM_HIP_MAX_COUNT_LEVELS cut-offs per motif");
+        if (thresholds.size() != n * levels)
+            throw std::invalid_argument("`levels` thresholds per motif");
+        std::vector<const lm_hip_pssm *> handles(n);
+        for (size_t i = 0; i < n; ++i)
+            handles[i] = pssms[i]->device(ctx_->ctx);
+        std::vector<uint32_t> flat(n * levels * records);
+        check(lm_hip_scan_count_seqset(ctx_->ctx, handles.data(), thresholds.data(), levels, n, set.handle(), flat.data()));
+        std::vector<std::vector<std::vector<uint32_t>>> out(n, std::vector<std::vector<uint32_t>>(levels));
+        for (size_t i = 0; i < n; ++i)
+            for (size_t l = 0; l < levels; ++l)
+                out[i][l].assign(flat.begin() + (i * levels + l) * records, flat.begin() + (i * levels + l + 1) * records);
+        return out;
+    }
 
     // ---- row-sharded jobs across the GPUs of a node -----------------------------------
     // Score::score_rows_into takes a row range so that a sequence can be cut (pli/mod.rs:72-78):

@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "background_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -386,6 +386,32 @@ class Pipeline:
         check(self._L.lm_hip_scan_best_seqset(self._h, batch.handles, n, seqset._h,
                                               raw.ctypes.data_as(C.POINTER(_ffi.SetBest)) if raw.size else None))
         return SetBest(raw.reshape(n, records), self.last_kernel if raw.size else "")
+
+    def scan_count_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], thresholds,
+                       seqset: "StripedSequenceSet") -> "SetCounts":
+        """How many windows of every motif reach its cut-offs in every record, in one call and without a hit list
+        (``lm_hip_scan_count_seqset``).  ``thresholds`` has shape ``(n,)`` or ``(n, levels)``, ``1 <= levels <= 4``: several
+        cut-offs of a motif cost one walk.  A window ``position + M <= len(record)`` (scan.rs:185-190) counts at a level
+        when ``score >= t`` in f32; NaN windows and NaN thresholds count nothing.  Of a ``MotifBatch`` only the handles are
+        used."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms)
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        n, records = len(batch), len(seqset)
+        ts = np.ascontiguousarray(thresholds, dtype=np.float32)
+        if ts.ndim == 1:
+            ts = ts.reshape(-1, 1)
+        if ts.ndim != 2 or ts.shape[0] != n:
+            raise ValueError("thresholds: one per motif, or one row of cut-offs per motif")
+        levels = ts.shape[1]
+        if not 1 <= levels <= _ffi.MAX_COUNT_LEVELS:
+            raise ValueError(f"{levels} cut-offs per motif: a call takes 1 ... {_ffi.MAX_COUNT_LEVELS}")
+        counts = np.zeros((n, levels, records), dtype=np.uint32)
+        check(self._L.lm_hip_scan_count_seqset(self._h, batch.handles, ts.ctypes.data_as(C.POINTER(C.c_float)), levels, n, seqset._h,
+                                               counts.ctypes.data_as(C.POINTER(C.c_uint32)) if counts.size else None))
+        lengths = seqset.lengths.reshape(1, -1)
+        rows = np.asarray([len(p) for p in batch.pssms], dtype=np.int64).reshape(-1, 1)
+        return SetCounts(counts, np.maximum(0, lengths - rows + 1), self.last_kernel if counts.size else "")
 
     def score_distributions(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"]) -> "ScoreDistributions":
         """The score distributions (pwm/dist.rs:51-226) of a whole motif list, built and kept on the device
@@ -1507,6 +1533,23 @@ class SetBest:
 
     def __len__(self) -> int:
         return self.raw.shape[0]
+
+
+class SetCounts:
+    """The result of ``Pipeline.scan_count_set``: ``counts`` -- ``(motifs, levels, records)`` uint32, the windows of a motif
+    in a record that reach a cut-off -- and ``windows`` -- ``(motifs, records)`` int64, the windows there are,
+    ``max(0, L_r - M_i + 1)``, made on the host from the record lengths; ``last_kernel`` names the kernel that ran last for
+    the call ("" when nothing ran)."""
+
+    def __init__(self, counts: np.ndarray, windows: np.ndarray, last_kernel: str = ""):
+        self.counts, self.windows, self.last_kernel = counts, windows, last_kernel
+
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        return self.counts.shape
+
+    def __len__(self) -> int:
+        return self.counts.shape[0]
 
 
 class ScoreDistributions:

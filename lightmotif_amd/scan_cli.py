@@ -27,6 +27,10 @@ Behaviour follows lightmotif-cli/src/main.rs:
 ``--best`` writes, instead of the hits above a threshold, ONE line per (sequence, strand, motif) that has a window: the
 best window of the motif in that record, the lowest position among equal scores (``Pipeline.scan_best_set``); thresholds
 play no part.
+``--counts`` writes, instead of the hits themselves, how many there are: ONE line per (sequence, strand, motif) that has a
+window, ``seq_index seq_name motif_index motif_name strand windows hits`` -- the windows of the motif in that record and
+how many of them reach the motif's threshold (``Pipeline.scan_count_set``: no hit list is made).  It needs one of ``-P``,
+``--abs-threshold``, ``--rel-threshold`` and excludes ``--best``, ``--matched`` and ``--site-matrices``.
 ``--pvalues device`` (the default) builds the score distributions of all motifs on the device
 (``Pipeline.score_distributions``): the thresholds of ``-P`` come from one call, and the ``pvalue`` column of a set from one
 call per strand on the set's hits.  ``--pvalues host`` is the per-motif, per-hit host code of ``dist.py``; the TSV is the
@@ -241,6 +245,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--reverse", action="store_true", help="also scan the reverse-complement matrices")
     ap.add_argument("--best", action="store_true",
                     help="write the best window of every motif in every record instead of the hits above a threshold")
+    ap.add_argument("--counts", action="store_true",
+                    help="write the number of hits of every motif in every record instead of the hits (needs -P, "
+                         "--abs-threshold or --rel-threshold)")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch-bases", type=int, default=DEFAULT_BATCH_BASES,
                     help="bases of sequence gathered into one resident set and scanned with one call per strand "
@@ -285,6 +292,11 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     print("Preparing motifs")
     if args.batch_bases < 1:
         ap.error("--batch-bases must be positive")
+    if args.counts:
+        if args.pvalue is None and args.abs_threshold is None and args.rel_threshold is None:
+            ap.error("--counts needs a threshold: one of -P, --abs-threshold, --rel-threshold")
+        if args.best or args.matched or args.site_matrices:
+            ap.error("--counts excludes --best, --matched and --site-matrices")
     pli = Pipeline.hip(args.device)
 
     def sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
@@ -335,11 +347,34 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     n_hits = 0
     with contextlib.ExitStack() as files:
         out = files.enter_context(open(args.output, "w"))
-        out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue" + ("\tmatched" if args.matched else "") + "\n")
+        if args.counts:
+            out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tstrand\twindows\thits\n")
+        else:
+            out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue" + ("\tmatched" if args.matched else "") + "\n")
         site_totals = [np.zeros((m, len(DNA_SYMBOLS)), dtype=np.int64) for m in lengths] if args.site_matrices else None
         composition = files.enter_context(open(args.composition, "w")) if args.composition else None
         if composition is not None:
             composition.write("seq_index\tseq_name\tlength\t" + "\t".join(DNA_SYMBOLS) + "\n")
+
+        def write_composition(first_index: int, names: List[str], seqset: StripedSequenceSet) -> None:
+            table = seqset.count_symbols().tolist()
+            for r, (name, length) in enumerate(zip(names, seqset.lengths.tolist())):
+                composition.write(f"{first_index + r + 1}\t{name}\t{length}\t" + "\t".join(map(str, table[r])) + "\n")
+
+        def write_counts(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
+            seqset.configure_wrap(max_m)                                   # main.rs:543
+            tables = [(strand, pli.scan_count_set(batch, thresholds, seqset)) for strand, batch in batches]
+            if composition is not None:
+                write_composition(first_index, names, seqset)
+            wrote = 0
+            for r, name in enumerate(names):
+                for strand, res in tables:
+                    windows, hits = res.windows[:, r].tolist(), res.counts[:, 0, r].tolist()
+                    for mi, (w, h) in enumerate(zip(windows, hits)):
+                        if w > 0:
+                            out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{strand}\t{w}\t{h}\n")
+                            wrote += 1
+            return wrote
 
         def write_set(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
             seqset.configure_wrap(max_m)                                   # main.rs:543
@@ -347,9 +382,7 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             # either strand looks the DIRECT matrix's distribution up (main.rs:335)
             pvalues = [None if dists is None else hit_pvalues(dists, motif, score) for _, (motif, _, score, _) in found]
             if composition is not None:
-                table = seqset.count_symbols().tolist()
-                for r, (name, length) in enumerate(zip(names, seqset.lengths.tolist())):
-                    composition.write(f"{first_index + r + 1}\t{name}\t{length}\t" + "\t".join(map(str, table[r])) + "\n")
+                write_composition(first_index, names, seqset)
             # the windows of the hits, read out of the resident set: one call per strand, whatever the number of hits
             matched = [None] * len(found)
             if args.matched or site_totals is not None:
@@ -377,12 +410,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             return wrote
 
         for first, names, seqset in sets():
-            n_hits += write_set(first, names, seqset)
+            n_hits += (write_counts if args.counts else write_set)(first, names, seqset)
         if site_totals is not None:
             if any(int(t.max(initial=0)) > 0xFFFFFFFF for t in site_totals):
                 raise OverflowError("--site-matrices: a site count exceeds the u32 of a count matrix")
             lmio.write([lmio.Record(r.id, r.description, CountMatrix(t)) for r, t in zip(records, site_totals)], args.site_matrices)
-    print(f"Wrote {n_hits} hits to {args.output}")
+    print(f"Wrote {n_hits} {'lines' if args.counts else 'hits'} to {args.output}")
     return 0
 
 

@@ -21,6 +21,10 @@ resident, the calls alone timed) and writes ``profiles/seqset_best_bench.json``:
       call that gave the answer before ``scan_best_set`` existed (a 16-byte hit for every window of every motif);
   B'  ``scan_best_set``;
   C'  ``scan_argmax_batch`` over the plain concatenation: the bare fused argmax, no segmentation -- not the answer.
+
+``--count`` measures the hits per (motif, record) on the same set at p = 1e-1 ... 1e-5 (``measure_count``: the list plus a
+``bincount`` per motif, ``scan_count_set``, and ``scan_best_set`` as the walk's floor) and writes
+``profiles/seqset_count_bench.json``.
 """
 from __future__ import annotations
 
@@ -229,6 +233,117 @@ def main_best(a):
     return 0 if res["answers_equal"] else 1
 
 
+COUNT_PVALUES = (1e-1, 1e-2, 1e-3, 1e-4, 1e-5)
+COUNT_LEVELS3 = (1e-1, 1e-2, 1e-3)
+
+
+def count_hits(res, n_records, cuts=None):
+    """A: ``(motifs, levels, records)`` counts from a ``SetHits``: per motif one ``bincount`` of the record column (with
+    ``cuts`` -- ``(motifs, levels)`` thresholds -- one per level, over the hits that reach it)."""
+    n = len(res)
+    out = np.zeros((n, 1 if cuts is None else cuts.shape[1], n_records), dtype=np.uint32)
+    for mi in range(n):
+        rec, _, val = res[mi]
+        if cuts is None:
+            out[mi, 0] = np.bincount(rec, minlength=n_records)
+        else:
+            for li in range(cuts.shape[1]):
+                out[mi, li] = np.bincount(rec[val >= cuts[mi, li]], minlength=n_records)
+    return out
+
+
+def alternate(ways, runs, warmup, untimed_first=("A",)):
+    """Medians of `runs` alternating calls of every way after `warmup` rounds; the ways of `untimed_first` follow an
+    untimed call of their own kind (the hit list is sized from the call before, as in measure())."""
+    times = {k: [] for k in ways}
+    for it in range(warmup + runs):
+        for k in sorted(ways):
+            if k in untimed_first:
+                ways[k]()
+            t0 = time.perf_counter()
+            ways[k]()
+            if it >= warmup:
+                times[k].append((time.perf_counter() - t0) * 1e3)
+    return {k: {"median": statistics.median(v), "min": min(v), "max": max(v), "all": [round(x, 3) for x in v]} for k, v in times.items()}
+
+
+def measure_count(pli, n_records, length, n_motifs, runs=5, warmup=1):
+    """Hits per (motif, record) at p = 1e-1 ... 1e-5 on one resident set, three legs per p, alternating, medians of `runs`
+    after `warmup`, the answers of A and B compared first:
+
+      A   ``scan_threshold_set`` at the thresholds + one ``bincount`` per motif: the cheapest way before ``scan_count_set``;
+      B   ``scan_count_set`` with one level;
+      C   ``scan_best_set`` of the same motifs: the same walk with another reduction, so B / C is the price of counting.
+
+    ``three_levels``: ``scan_count_set`` at (1e-1, 1e-2, 1e-3) in one call (B3) against the list at 1e-1 plus the three
+    counts on the host (A3).  ``crossover_p``: the largest p of the sweep at which A is faster than B (None: nowhere)."""
+    pssms, _ = load_motifs(n_motifs)
+    lengths = [len(p) for p in pssms]
+    max_m = max(lengths)
+    _, joined = make_records(n_records, length)
+    offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(length)
+    seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+    seqset.configure_wrap(max_m)
+    dists = pli.score_distributions(pssms)
+    batch = pli.prepare_batch(pssms)
+    kernels = set()
+
+    def way_c():
+        return pli.scan_best_set(batch, seqset)
+
+    sweep = []
+    for p in COUNT_PVALUES:
+        ts = dists.thresholds(p)
+        listed = pli.prepare_batch(pssms, ts)
+
+        def way_a():
+            return count_hits(pli.scan_threshold_set(listed, None, seqset), n_records)
+
+        def way_b():
+            res = pli.scan_count_set(batch, ts, seqset)
+            kernels.add(res.last_kernel)
+            return res.counts
+
+        a, b = way_a(), way_b()
+        ms = alternate({"A": way_a, "B": way_b, "C": way_c}, runs, warmup)
+        sweep.append({"p": p, "answers_equal": bool(np.array_equal(a, b)), "hits": int(b.sum(dtype=np.int64)), "ms": ms,
+                      "A_over_B": ms["A"]["median"] / ms["B"]["median"], "B_over_C": ms["B"]["median"] / ms["C"]["median"]})
+
+    cuts = np.stack([dists.thresholds(p) for p in COUNT_LEVELS3], axis=1)
+    loosest = pli.prepare_batch(pssms, cuts.min(axis=1))
+
+    def way_a3():
+        return count_hits(pli.scan_threshold_set(loosest, None, seqset), n_records, cuts)
+
+    def way_b3():
+        return pli.scan_count_set(batch, cuts, seqset).counts
+
+    a3, b3 = way_a3(), way_b3()
+    ms3 = alternate({"A": way_a3, "B": way_b3}, runs, warmup)
+    three = {"p": list(COUNT_LEVELS3), "answers_equal": bool(np.array_equal(a3, b3)), "ms": {"A3": ms3["A"], "B3": ms3["B"]},
+             "A3_over_B3": ms3["A"]["median"] / ms3["B"]["median"]}
+    a_wins = [row["p"] for row in sweep if row["ms"]["A"]["median"] < row["ms"]["B"]["median"]]
+    windows = int(sum(max(0, length - m + 1) for m in lengths)) * n_records
+    return {"records": n_records, "record_length": length, "motifs": len(pssms), "motif_lengths": lengths, "runs": runs, "warmup": warmup,
+            "windows": windows, "kernel": sorted(kernels), "answers_equal": all(r["answers_equal"] for r in sweep) and three["answers_equal"],
+            "sweep": sweep, "three_levels": three, "crossover_p": max(a_wins) if a_wins else None}
+
+
+def main_count(a):
+    pli = lm.Pipeline.hip(0)
+    res = measure_count(pli, 2_000, 500, 8, runs=a.runs, warmup=2)
+    out = a.out if a.out != str(ROOT / "profiles" / "seqset_bench.json") else str(ROOT / "profiles" / "seqset_count_bench.json")
+    result = {"tool": "tools/seqset_bench.py --count", "device": "MI355X (gfx950)", "case": res}
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    for row in res["sweep"]:
+        print(json.dumps({"p": row["p"], "hits": row["hits"], "A_ms": round(row["ms"]["A"]["median"], 3), "B_ms": round(row["ms"]["B"]["median"], 3),
+                          "C_ms": round(row["ms"]["C"]["median"], 3), "A_over_B": round(row["A_over_B"], 2), "B_over_C": round(row["B_over_C"], 2)}))
+    print(json.dumps({"A3_over_B3": res["three_levels"]["A3_over_B3"], "crossover_p": res["crossover_p"], "answers_equal": res["answers_equal"],
+                      "wrote": out}))
+    return 0 if res["answers_equal"] else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="both", choices=["i", "ii", "both"])
@@ -237,9 +352,12 @@ def main():
     ap.add_argument("--loop-records-ii", type=int, default=500, help="records the loop of case (ii) runs over (scaled to 50 000)")
     ap.add_argument("--out", default=str(ROOT / "profiles" / "seqset_bench.json"))
     ap.add_argument("--best", action="store_true", help="the best hit per record (measure_best) -> profiles/seqset_best_bench.json")
+    ap.add_argument("--count", action="store_true", help="hits per (motif, record) (measure_count) -> profiles/seqset_count_bench.json")
     a = ap.parse_args()
     if a.best:
         return main_best(a)
+    if a.count:
+        return main_count(a)
     pli = lm.Pipeline.hip(0)
     result = {"tool": "tools/seqset_bench.py", "device": "MI355X (gfx950)", "cases": {}}
     for name in (["i", "ii"] if a.case == "both" else [a.case]):
