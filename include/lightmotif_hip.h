@@ -507,8 +507,9 @@ int lm_hip_scan_threshold_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssm
  *               of only -inf windows answers (-inf, 0)), position = the LOWEST record-relative position holding it
  * i.e. among record r's hits in lm_hip_scan_threshold_seqset's list for a threshold of -inf, the greatest score and
  * the first of those in list order.  Deterministic, identical from call to call and with the prefilter on or off: the
- * route is exact f32 throughout (csrc/seqset_best.hip; lm_hip_ctx_last_kernel names the kernel that ran last,
- * `seqset_best_fused<M>` up to M = 36, `seqset_best_generic` beyond).
+ * route is exact f32 throughout (csrc/seqset_best.hip on the record walk of csrc/seqset_walk.hpp;
+ * lm_hip_ctx_last_kernel names the kernel that ran last, `seqset_best_fused<M>` up to M = 36, `seqset_best_generic`
+ * beyond).
  * This deliberately is NOT Maximum::argmax (pli/mod.rs:135-155) on the record's own score matrix: that rule also scans
  * the cells of the padded tail and takes the LAST maximal cell in (row, col) order.  The two agree -- same score, and
  * position = col * rows + row of the record striped alone -- when the maximum over the valid windows is unique and the
@@ -537,8 +538,8 @@ int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, si
  * lm_hip_scan_threshold_seqset's list for motif i at t.  A motif with no window anywhere (no rows, or longer than the
  * sequence) gives zeros.
  * Deterministic, identical from call to call and with the prefilter on or off: the route is exact f32 throughout and its
- * merge is a sum of integers (csrc/seqset_count.hip: the walk of lm_hip_scan_best_seqset with per-lane counters that
- * reach the cells through 32-bit atomic adds; lm_hip_ctx_last_kernel names `seqset_count_fused<M>` up to M = 36,
+ * merge is a sum of integers (csrc/seqset_count.hip: the record walk of csrc/seqset_walk.hpp with per-lane counters
+ * that reach the cells through 32-bit atomic adds; lm_hip_ctx_last_kernel names `seqset_count_fused<M>` up to M = 36,
  * `seqset_count_generic` beyond).
  * Measured on one MI355X (tools/seqset_bench.py --count, profiles/seqset_count_bench.json; 2 000 records x 500 bp x 8
  * JASPAR motifs, the set resident, medians of 15 alternating runs), against lm_hip_scan_threshold_seqset at the same

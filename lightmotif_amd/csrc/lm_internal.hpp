@@ -244,7 +244,8 @@ struct lm_hip_ctx {
 };
 
 namespace lm {
-// at every place a launcher out of the kernel registry (score_registry.hpp) or the fused table of seqset_best.hip is called
+// at every place a launcher out of the kernel registry (score_registry.hpp) or a tallied table of fused walk kernels
+// (seqset_walk_launch.hpp: seqset_best.hip's) is called
 inline void tally_launch(lm_hip_ctx *ctx, int family, bool wide, size_t m, int slot = 0)
 {
     if (ctx->tally_launches)
@@ -412,6 +413,9 @@ struct lm_hip_seq {
 
 // Many records resident as ONE striped sequence (seqset.hip): `seq` is StripedSequence of the joined text, record r is
 // symbols [offsets[r], offsets[r + 1]) of it; the table lives on the device as well (64-bit entries).
+// offsets (8 B each) a workgroup stages in LDS: sets of up to 4 095 records (seqset.hip, seqset_walk_launch.hpp)
+constexpr unsigned kSetLdsOffsets = 4096;
+
 struct lm_hip_seqset {
     int device = 0;
     lm_hip_seq *seq = nullptr;

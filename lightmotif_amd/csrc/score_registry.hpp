@@ -50,7 +50,8 @@ PrefilterLauncher score_c32_prefilter_lookup(int M, bool wide = false, bool bloc
 PrefilterLauncher score_c32_prefilter2_lookup(int M, int K = 5);
 PrefilterMultiLauncher score_c32_prefilter2_multi_lookup(int M);
 ScoreU8Launcher score_c32_lookup_u8(int M, bool pairs, bool wide);
-// seqset_best.hip keeps a table of its own: seqset_best_fused<M>, M = 1 ... kMaxFastM (nullptr: no such kernel)
+// seqset_best.hip keeps a table of its own (WalkKernels, seqset_walk_launch.hpp): seqset_best_fused<M>, M = 1 ... kMaxFastM
+// (nullptr: no such kernel)
 const void *seqset_best_fused_row(int M);
 
 }  // namespace lm

@@ -29,7 +29,6 @@ namespace lm {
 namespace {
 
 constexpr unsigned long long kLowMask = (1ull << 40) - 1;
-constexpr int kSegLdsEntries = 4096;  // offsets (8 B each) a workgroup stages: sets of up to 4 095 records
 constexpr int kWavesPerBlock = kBlock / 64;
 
 // largest r in [0, n] with off[r] <= p (off[0] == 0; r == n: p lies behind the last record).  `hint` is the record of
@@ -75,7 +74,7 @@ __global__ __launch_bounds__(kBlock) void seqset_cut(
     unsigned long long *__restrict__ starts, lm_hip_set_hit *__restrict__ out, lm_hip_set_hit *__restrict__ pre_out,
     const unsigned long long pre)
 {
-    __shared__ unsigned long long s_off[LDS ? kSegLdsEntries : 1];
+    __shared__ unsigned long long s_off[LDS ? kSetLdsOffsets : 1];
     __shared__ unsigned long long s_part[kBlock];
     if (LDS) {
         for (unsigned i = threadIdx.x; i <= n_records; i += kBlock)
@@ -185,7 +184,7 @@ int launch_segment_cut(hipStream_t st, const HitRecord *ordered, const unsigned 
 {
     const char *job_m = static_cast<const char *>(seg.d_job_m);
     const unsigned long long stride = seg.job_m_stride;
-    if (seg.n_records + 1 <= (unsigned long long)kSegLdsEntries) {
+    if (seg.n_records + 1 <= (unsigned long long)kSetLdsOffsets) {
         hipLaunchKernelGGL((seqset_cut<false, true>), dim3(grid), dim3(kBlock), 0, st, ordered, count_ptr, room, njobs, seg.d_offsets,
                            seg.n_records, job_m, stride, wave_counts, starts, out, pre_out, pre);
         hipLaunchKernelGGL((seqset_cut<true, true>), dim3(grid), dim3(kBlock), 0, st, ordered, count_ptr, room, njobs, seg.d_offsets,

@@ -6,42 +6,19 @@
 // StripedSequence (seqset.hip); the windows of record r are positions p with p + M <= len(r) (scan.rs:185-190, per
 // RECORD) and each scores as `score_into` scores it: M sequential f32 adds from +0.0 in row order (pli/mod.rs:96-105).
 //
-// In the striped layout a lane that walks down one column meets CONSECUTIVE positions of the concatenation, so a record
-// is a run of rows and its boundaries come to the lane:
-//
-//   seqset_best_fused<M>   M <= kMaxFastM.  A lane owns rows [r0, r1) of one column.  It loads one symbol per row and
-//                          keeps the M windows that symbol belongs to in M rotating accumulators (window w receives
-//                          weight row j at step w + j: the reference's add order); the window that just received its
-//                          last row is complete.  The loop is unrolled M steps, so every accumulator index is a
-//                          compile-time constant and nothing is indexed dynamically.
-//   seqset_best_generic    any M: the same walk, every window summed from scratch over its M symbols.
-//
-// Both keep, per lane, the current record (find_record once, then advanced), the position of the next EVENT and a
-// running (score, position).  The next event is the first window of the record that no longer fits
-// (offsets[r + 1] - M + 1) and then the record's end: a common step pays one compare against it.  Windows between the
-// two are scored and never compete (the straddlers).  A lane's run ends at the bottom of its column; the windows there
-// read the wrap rows, i.e. the top of the next column, which is how a record that crosses a column boundary stays
-// correct; the last column's wrap rows hold padding and those windows straddle or lie behind the last record.
-//
-// At a record's end and at the end of its run a lane MERGES its partial into slot (job, record) with one 64-bit
-// atomicMax on
+// The walk down the records, the kernel bodies (seqset_best_fused<M> for M <= kMaxFastM, seqset_best_generic for any M)
+// and the launcher are those of seqset_walk.hpp / seqset_walk_launch.hpp; this unit holds the reduction.  A lane keeps a
+// running (score, position); at a record's end and at the end of its run it MERGES its partial into slot (job, record)
+// with one 64-bit atomicMax on
 //       order-preserving map of the f32 bits << 32 | 0xFFFFFFFF - position in the record
 // so the greatest score wins and, among equal scores, the lowest position: the merge is order-independent and the answer
 // deterministic.  NaN windows never compete, -inf windows do; a slot nobody merged into stays 0 ("none": no valid key is
 // 0).  seqset_best_finalize turns slots into lm_hip_set_best.
-//
-// Offsets of sets of up to 4 095 records are staged in LDS, larger tables are read from global memory.
-#include <algorithm>
-#include <cstring>
-
-#include "score_launch.hpp"
+#include "seqset_walk_launch.hpp"
 
 namespace lm {
 
 namespace best {  // (named: tools/kernel_regs.py lists kernels by their demangled names)
-
-constexpr unsigned kBestLdsOffsets = 4096;  // offsets (8 B each) a workgroup stages, as seqset_cut does
-constexpr unsigned long long kNoEnd = ~0ull;
 
 struct BestJob {
     const float *dense;             // M x K weights, row-major
@@ -58,42 +35,24 @@ __device__ __forceinline__ float unordered_bits(unsigned o)
     return __uint_as_float((o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o);
 }
 
-// What a lane carries down its run of consecutive positions.
-struct Segmenter {
-    const unsigned long long *off;  // n + 1 offsets (LDS or global)
-    unsigned long long n;           // records
-    unsigned long long m;           // motif length
-    unsigned long long *slots;      // of this job
-    unsigned long long rec, start, end;
-    unsigned long long next;        // position of the next event
-    bool competing;                 // windows before `next` lie inside the record
-    float best;                     // NaN: none yet
+struct BestReducer {
+    typedef unsigned long long Slot;
+    float best;  // NaN: none yet
     unsigned long long best_pos;
 
-    __device__ __forceinline__ void enter(unsigned long long r)
-    {
-        rec = r;
-        start = off[r < n ? r : n];
-        end = r < n ? off[r + 1] : kNoEnd;  // behind the last record: padding, nothing fits and nothing ends
-        competing = true;
-        next = (r < n && end - start >= m) ? end - m + 1 : start;
-    }
-    __device__ __forceinline__ void begin(unsigned long long p)
+    __device__ __forceinline__ void begin(const BestJob &)
     {
         best = __uint_as_float(0x7FC00000u);
         best_pos = 0;
-        // largest r with off[r] <= p (seqset.hip: find_record, without a hint)
-        unsigned long long lo = 0, hi = n + 1;
-        while (lo < hi) {
-            const unsigned long long mid = lo + (hi - lo) / 2;
-            if (off[mid] <= p)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        enter(lo - 1);
     }
-    __device__ __forceinline__ void flush()
+    __device__ __forceinline__ void window(unsigned long long p, float v, bool inside)
+    {
+        if (inside && v == v && !(v <= best)) {  // strictly greater, or the first: the lowest position of a tie stays
+            best = v;
+            best_pos = p;
+        }
+    }
+    __device__ __forceinline__ void flush(Slot *slots, unsigned long long rec, unsigned long long start, unsigned long long)
     {
         if (best == best) {
             const unsigned long long key = ((unsigned long long)ordered_bits(best) << 32) |
@@ -102,62 +61,8 @@ struct Segmenter {
             best = __uint_as_float(0x7FC00000u);
         }
     }
-    __device__ __forceinline__ void event(unsigned long long p)
-    {
-        while (p >= next) {
-            if (competing) {  // the first window that no longer fits: straddlers up to the record's end
-                competing = false;
-                next = end;
-            } else {
-                flush();
-                enter(rec + 1);
-            }
-        }
-    }
-    // the window at position p (ascending from call to call) scored v; `live` off: not a window of this lane's run.
-    // (v is consumed on the straight path, by selects: behind a branch the compiler would sink the adds that make it
-    // to here and keep every weight row of the last M steps in registers instead of M accumulators)
-    __device__ __forceinline__ void take(unsigned long long p, float v, bool live = true)
-    {
-        if (__builtin_expect(live && p >= next, 0))
-            event(p);
-        if (live && competing && v == v && !(v <= best)) {  // strictly greater, or the first: the lowest position of a tie stays
-            best = v;
-            best_pos = p;
-        }
-    }
 };
 
-// dynamic LDS: [weights, 16-byte padded][offsets when they are staged]
-extern __shared__ __attribute__((aligned(16))) char s_dyn[];
-
-__device__ __forceinline__ const unsigned long long *stage_offsets(char *lds, const unsigned long long *g_offsets,
-                                                                   unsigned long long n_records, int in_lds)
-{
-    if (!in_lds)
-        return g_offsets;
-    unsigned long long *s_off = reinterpret_cast<unsigned long long *>(lds);
-    for (unsigned i = threadIdx.x; i <= (unsigned)n_records; i += kBlock)
-        s_off[i] = g_offsets[i];
-    return s_off;
-}
-
-template <int MP>
-__device__ __forceinline__ void fetch_weights(float (&w)[MP], const float *row)
-{
-    const float4 *wr = reinterpret_cast<const float4 *>(row);
-#pragma unroll
-    for (int q = 0; q < MP / 4; ++q) {
-        const float4 v = wr[q];
-        w[4 * q] = v.x;
-        w[4 * q + 1] = v.y;
-        w[4 * q + 2] = v.z;
-        w[4 * q + 3] = v.w;
-    }
-}
-
-// grid.x: workgroups of kBlock lanes, lane L = blockIdx.x * kBlock + threadIdx.x owns column L % cols of stream L / cols
-// (rows [stream * T, stream * T + T)); grid.y: the jobs of one motif length.
 template <int M>
 __global__ __launch_bounds__(kBlock) void seqset_best_fused(
     const uint8_t *__restrict__ seq, const unsigned long long stride, const unsigned cols, const unsigned long long rows,
@@ -165,110 +70,17 @@ __global__ __launch_bounds__(kBlock) void seqset_best_fused(
     const unsigned long long *__restrict__ g_offsets, const unsigned long long n_records, const int offsets_in_lds,
     const unsigned long long T, unsigned long long *__restrict__ slots)
 {
-    constexpr int TS = table_stride(M, 0);  // floats per symbol, a multiple of 4: 16-byte aligned rows
-    constexpr int MP = 4 * ((M + 3) / 4);
-    const BestJob job = jobs[blockIdx.y];
-    float *s_w = reinterpret_cast<float *>(s_dyn);  // s_w[s * TS + j] = weights[j][s], zero padded
-    const unsigned wbytes = (K * TS * 4u + 15u) & ~15u;
-    for (unsigned i = threadIdx.x; i < K * TS; i += kBlock) {
-        const unsigned s = i / TS, j = i % TS;
-        s_w[i] = j < (unsigned)M ? job.dense[j * K + s] : 0.0f;
-    }
-    Segmenter sg;
-    sg.off = stage_offsets(s_dyn + wbytes, g_offsets, n_records, offsets_in_lds);
-    __syncthreads();
-
-    const unsigned long long lane = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
-    const unsigned long long col = lane % cols, r0 = (lane / cols) * T;
-    if (r0 >= rows)
-        return;
-    const unsigned long long r1 = r0 + T < rows ? r0 + T : rows;
-    sg.n = n_records;
-    sg.m = M;
-    sg.slots = slots + job.slot_base;
-    sg.begin(col * rows + r0);
-
-    // step t reads row r0 + t; the window it completes started at row r0 + t - (M - 1): position base + t
-    const unsigned long long total = (r1 - r0) + (M - 1);
-    const long long base = (long long)(col * rows + r0) - (M - 1);
-    const unsigned long long last_row = rows_total - 1;  // rows + wrap - 1 >= r1 + M - 2: clamped reads are never used
-    const uint8_t *sp = seq + col;
-    float acc[M];
-#pragma unroll
-    for (int j = 0; j < M; ++j)
-        acc[j] = 0.0f;
-    for (unsigned long long g = 0; g < total; g += M) {
-        unsigned sym[M];
-#pragma unroll
-        for (int s = 0; s < M; ++s) {
-            const unsigned long long row = r0 + g + s;
-            sym[s] = sp[(row < last_row ? row : last_row) * stride];
-        }
-        // the weight rows of step s + 1 are fetched while step s adds, and no further ahead: the scheduler otherwise
-        // hoists the rows of all M steps (M * M registers)
-        float w[2][MP];
-        fetch_weights<MP>(w[0], s_w + sym[0] * TS);
-#pragma unroll
-        for (int s = 0; s < M; ++s) {
-            if (s + 1 < M)
-                fetch_weights<MP>(w[(s + 1) & 1], s_w + sym[s + 1] * TS);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int j = 0; j < M; ++j)
-                acc[(s - j + M) % M] = acc[(s - j + M) % M] + w[s & 1][j];  // window (t - j) receives row j
-            // pins the sums here: the compiler otherwise sinks each window's adds to the step that completes it, behind
-            // the event branches, and keeps the weight rows of M steps alive instead of M accumulators
-#pragma unroll
-            for (int j = 0; j < M; ++j)
-                asm volatile("" : "+v"(acc[j]));
-            const unsigned long long t = g + s;
-            const float v = acc[(s + 1) % M];  // the window that started M - 1 steps ago is complete
-            acc[(s + 1) % M] = 0.0f;
-            sg.take((unsigned long long)(base + (long long)t), v, t >= (unsigned long long)(M - 1) && t < total);
-        }
-    }
-    sg.flush();
+    walk_fused<M, table_stride(M, 0), BestReducer>(seq, stride, cols, rows, rows_total, K, jobs, g_offsets, n_records, offsets_in_lds, T,
+                                                   slots);
 }
 
-// Any motif length: every window summed over its own M symbols (weights in LDS when they fit, `w_in_lds`).
 __global__ __launch_bounds__(kBlock) void seqset_best_generic(
     const uint8_t *__restrict__ seq, const unsigned long long stride, const unsigned cols, const unsigned long long rows,
     const unsigned M, const unsigned K, const int w_in_lds, const BestJob *__restrict__ jobs,
     const unsigned long long *__restrict__ g_offsets, const unsigned long long n_records, const int offsets_in_lds,
     const unsigned long long T, unsigned long long *__restrict__ slots)
 {
-    const BestJob job = jobs[blockIdx.y];
-    float *s_w = reinterpret_cast<float *>(s_dyn);
-    const unsigned wbytes = w_in_lds ? (M * K * 4u + 15u) & ~15u : 0u;
-    if (w_in_lds)
-        for (unsigned i = threadIdx.x; i < M * K; i += kBlock)
-            s_w[i] = job.dense[i];
-    Segmenter sg;
-    sg.off = stage_offsets(s_dyn + wbytes, g_offsets, n_records, offsets_in_lds);
-    __syncthreads();
-
-    const unsigned long long lane = (unsigned long long)blockIdx.x * kBlock + threadIdx.x;
-    const unsigned long long col = lane % cols, r0 = (lane / cols) * T;
-    if (r0 >= rows)
-        return;
-    const unsigned long long r1 = r0 + T < rows ? r0 + T : rows;
-    sg.n = n_records;
-    sg.m = M;
-    sg.slots = slots + job.slot_base;
-    sg.begin(col * rows + r0);
-    const uint8_t *sp = seq + col;
-    for (unsigned long long row = r0; row < r1; ++row) {  // rows row .. row + M - 1 <= rows + wrap - 1
-        const uint8_t *s = sp + row * stride;
-        float v = 0.0f;
-        if (w_in_lds)
-            for (unsigned j = 0; j < M; ++j)
-                v = v + s_w[j * K + s[j * stride]];
-        else
-            for (unsigned j = 0; j < M; ++j)
-                v = v + job.dense[j * K + s[j * stride]];
-        sg.take(col * rows + row, v);
-    }
-    sg.flush();
+    walk_generic<BestReducer>(seq, stride, cols, rows, M, K, w_in_lds, jobs, g_offsets, n_records, offsets_in_lds, T, slots);
 }
 
 __global__ __launch_bounds__(kBlock) void seqset_best_finalize(const unsigned long long *__restrict__ slots,
@@ -285,141 +97,22 @@ __global__ __launch_bounds__(kBlock) void seqset_best_finalize(const unsigned lo
     out[i] = b;
 }
 
-typedef void (*FusedKernel)(const uint8_t *, unsigned long long, unsigned, unsigned long long, unsigned long long, unsigned,
-                            const BestJob *, const unsigned long long *, unsigned long long, int, unsigned long long,
-                            unsigned long long *);
-template <int M>
-struct FusedTable {
-    static void fill(FusedKernel *t, const char **names)
-    {
-        static char name[32];
-        snprintf(name, sizeof name, "seqset_best_fused<%d>", M);
-        t[M] = seqset_best_fused<M>;
-        names[M] = name;
-        FusedTable<M - 1>::fill(t, names);
-    }
+struct BestWalk {
+    typedef BestJob Job;
+    typedef BestReducer::Slot Slot;
+    static constexpr const char *kName = "seqset_best";
+    static constexpr int kTally = LM_HIP_FAMILY_BEST_FUSED;
+    template <int M>
+    static constexpr auto fused() { return seqset_best_fused<M>; }
+    static constexpr auto generic() { return seqset_best_generic; }
 };
-template <>
-struct FusedTable<0> {
-    static void fill(FusedKernel *, const char **) {}
-};
-
-struct Fused {
-    FusedKernel fn[kMaxFastM + 1] = {};
-    const char *name[kMaxFastM + 1] = {};
-    Fused() { FusedTable<kMaxFastM>::fill(fn, name); }
-};
-const Fused &fused()
-{
-    static const Fused f;
-    return f;
-}
-
-constexpr size_t kBestBlockBytes = (size_t)256 << 20;  // slots + results of one group of motifs on the device
 
 }  // namespace best
 using namespace best;
 
 const void *seqset_best_fused_row(int M)
 {
-    return (M >= 1 && M <= kMaxFastM) ? reinterpret_cast<const void *>(fused().fn[M]) : nullptr;
-}
-
-// Rows per lane: long enough that the M - 1 fill steps of a run cost little, short enough that the `njobs` jobs of the
-// call put a few wavefronts on every SIMD.
-static unsigned long long best_rows_per_lane(const lm_hip_ctx *ctx, const lm_hip_seq *seq, size_t m, size_t njobs)
-{
-    if (ctx->rows_per_stream)
-        return ctx->rows_per_stream;
-    const unsigned long long cells = (unsigned long long)seq->rows * seq->cols * njobs;
-    const unsigned long long lanes = (unsigned long long)ctx->num_cus * 512;
-    return std::min<unsigned long long>(std::max<unsigned long long>({4ull * m, cells / lanes, 16ull}), 4096ull);
-}
-
-int launch_seqset_best(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const char *degenerate, size_t n,
-                       const lm_hip_seqset *set, lm_hip_set_best *best)
-{
-    const lm_hip_seq *seq = set->seq;
-    const size_t records = set->offsets.size() - 1;
-    const bool off_lds = records + 1 <= kBestLdsOffsets;
-    const size_t off_bytes = off_lds ? (records + 1) * sizeof(unsigned long long) : 0;
-    const size_t per_job = records * (sizeof(unsigned long long) + sizeof(lm_hip_set_best));
-    const size_t group = std::max<size_t>(1, std::min<size_t>(n, kBestBlockBytes / std::max<size_t>(per_job, 1)));
-    const size_t head = (group * sizeof(BestJob) + 255) & ~(size_t)255;
-    LM_TRY(ctx->scratch.reserve(head + group * per_job));
-    char *block = static_cast<char *>(ctx->scratch.ptr);
-    BestJob *d_jobs = reinterpret_cast<BestJob *>(block);
-    unsigned long long *d_slots = reinterpret_cast<unsigned long long *>(block + head);
-    std::vector<BestJob> table;
-    std::vector<ScoreArgs> args;
-    for (size_t c0 = 0; c0 < n; c0 += group) {
-        const size_t c1 = std::min(n, c0 + group), nc = c1 - c0;
-        lm_hip_set_best *d_out = reinterpret_cast<lm_hip_set_best *>(d_slots + nc * records);
-        // the live jobs of this group of motifs, in launch order: JobGroups of one motif length each (grid.y)
-        args.clear();
-        std::vector<size_t> caller;  // caller index - c0 of args[i]
-        for (size_t i = c0; i < c1; ++i)
-            if (!degenerate[i]) {
-                args.push_back(ScoreArgs{pssms[i], seq->d_data, seq->stride, seq->cols, 0, seq->rows, nullptr, 0});
-                caller.push_back(i - c0);
-            }
-        const std::vector<JobGroup> groups = group_jobs(ctx, args.data(), args.size(), [&](size_t i) {
-            return args[i].pssm->m <= (size_t)kMaxFastM ? KIND_EXACT : KIND_GENERIC;
-        });
-        table.clear();
-        std::vector<size_t> first(groups.size());
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            first[gi] = table.size();
-            for (size_t i : groups[gi].idx)
-                table.push_back(BestJob{args[i].pssm->d_dense, (unsigned long long)caller[i] * records});
-        }
-        LM_HIP_TRY(hipMemsetAsync(d_slots, 0, nc * records * sizeof(unsigned long long), ctx->stream));
-        if (!table.empty()) {
-            const size_t tbytes = table.size() * sizeof(BestJob);
-            if (BestJob *pin = pinned_at<BestJob>(ctx, kPinUploadHead, table.size())) {
-                memcpy(pin, table.data(), tbytes);
-                LM_HIP_TRY(hipMemcpyAsync(d_jobs, pin, tbytes, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                LM_HIP_TRY(hipMemcpy(d_jobs, table.data(), tbytes, hipMemcpyHostToDevice));
-            }
-        }
-        BatchStreams streams(ctx, groups.size());
-        LM_TRY(streams.fork());
-        for (size_t gi = 0; gi < groups.size(); ++gi) {
-            const JobGroup &g = groups[gi];
-            const lm_hip_pssm *p = args[g.idx[0]].pssm;
-            const unsigned long long T = best_rows_per_lane(ctx, seq, p->m, args.size());
-            const unsigned long long lanes = ((unsigned long long)seq->rows + T - 1) / T * seq->cols;
-            const dim3 grid((unsigned)((lanes + kBlock - 1) / kBlock), (unsigned)g.idx.size());
-            hipStream_t st = streams.next();
-            if (g.kind == KIND_EXACT) {
-                const size_t lds = (((size_t)p->k * table_stride((int)p->m, 0) * 4 + 15) & ~(size_t)15) + off_bytes;
-                tally_launch(ctx, LM_HIP_FAMILY_BEST_FUSED, false, p->m);
-                hipLaunchKernelGGL(fused().fn[p->m], grid, dim3(kBlock), lds, st, seq->d_data, (unsigned long long)seq->stride,
-                                   (unsigned)seq->cols, (unsigned long long)seq->rows, (unsigned long long)(seq->rows + seq->wrap),
-                                   (unsigned)p->k, d_jobs + first[gi], set->d_offsets, (unsigned long long)records, (int)off_lds, T,
-                                   d_slots);
-                ctx->last_kernel = fused().name[p->m];
-            } else {
-                const size_t wbytes = p->m * p->k * sizeof(float);
-                const int w_lds = wbytes + off_bytes <= 60 * 1024;
-                const size_t lds = std::max<size_t>((w_lds ? (wbytes + 15) & ~(size_t)15 : 0) + off_bytes, 16);
-                hipLaunchKernelGGL(seqset_best_generic, grid, dim3(kBlock), lds, st, seq->d_data, (unsigned long long)seq->stride,
-                                   (unsigned)seq->cols, (unsigned long long)seq->rows, (unsigned)p->m, (unsigned)p->k, w_lds,
-                                   d_jobs + first[gi], set->d_offsets, (unsigned long long)records, (int)off_lds, T, d_slots);
-                ctx->last_kernel = "seqset_best_generic";
-            }
-            LM_HIP_TRY(hipGetLastError());
-        }
-        LM_TRY(streams.join());
-        const unsigned long long count = (unsigned long long)nc * records;
-        hipLaunchKernelGGL(seqset_best_finalize, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_slots,
-                           count, d_out);
-        LM_HIP_TRY(hipGetLastError());
-        LM_HIP_TRY(hipMemcpyAsync(best + c0 * records, d_out, count * sizeof(lm_hip_set_best), hipMemcpyDeviceToHost, ctx->stream));
-        LM_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
-    return LM_HIP_OK;
+    return (M >= 1 && M <= kMaxFastM) ? reinterpret_cast<const void *>(WalkKernels<BestWalk>::get().fn[M]) : nullptr;
 }
 
 }  // namespace lm
@@ -431,28 +124,22 @@ extern "C" int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const
 {
     if (!ctx || !set || (n && !pssms))
         return fail(LM_HIP_ERR_BAD_ARGS, "scan_best_seqset: null argument");
-    const lm_hip_seq *seq = set->seq;
-    const size_t records = set->offsets.size() - 1;
-    if (n && records && !best)
-        return fail(LM_HIP_ERR_BAD_ARGS, "scan_best_seqset: null result array");
-    std::vector<char> degenerate(n, 0);
-    for (size_t i = 0; i < n; ++i) {  // as lm_hip_scan_threshold_seqset: alphabet, then wrap (avx2.rs:832-837)
-        if (pssms[i])
-            LM_TRY(check_alphabet("scan_best_seqset", pssms[i]->k, seq));
-        LM_TRY(check_score_args(pssms[i], seq->rows + seq->wrap, seq->stride, seq->cols, seq->wrap, 0, seq->rows));
-        degenerate[i] = seq->length < pssms[i]->m || seq->rows == 0 || pssms[i]->m == 0;  // pli/mod.rs:85-88: no scores
-    }
-    if (n == 0 || records == 0)
+    std::vector<char> degenerate;
+    bool run;
+    LM_TRY(check_walk_call("scan_best_seqset", pssms, n, set, best, sizeof(lm_hip_set_best), 0, "the merge addresses", degenerate, &run));
+    if (!run)
         return LM_HIP_OK;
-    if (seq->length >> 32)  // the merge key holds a record-relative position in 32 bits
-        for (size_t r = 0; r < records; ++r)
-            if ((set->offsets[r + 1] - set->offsets[r]) >> 32)
-                return fail(LM_HIP_ERR_CAPACITY, "scan_best_seqset: record %zu holds %llu symbols, the merge addresses 2^32 - 1", r,
-                            (unsigned long long)(set->offsets[r + 1] - set->offsets[r]));
-    if (records > (~(size_t)0 / sizeof(lm_hip_set_best)) / n)
-        return fail(LM_HIP_ERR_CAPACITY, "scan_best_seqset: %zu motifs x %zu records overflow the result's size", n, records);
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    DeviceGuard guard(ctx->device);
-    ScratchTrim trim(ctx);
-    return launch_seqset_best(ctx, pssms, degenerate.data(), n, set, best);
+    const size_t records = set->offsets.size() - 1;  // a job: its slots, then its results
+    return launch_walk<BestWalk>(
+        ctx, pssms, degenerate.data(), n, set, records, records * (sizeof(unsigned long long) + sizeof(lm_hip_set_best)),
+        [&](size_t i, unsigned long long slot_base) { return BestJob{pssms[i]->d_dense, slot_base}; },
+        [&](size_t c0, size_t nc, unsigned long long *d_slots) {
+            const unsigned long long count = (unsigned long long)nc * records;
+            lm_hip_set_best *d_out = reinterpret_cast<lm_hip_set_best *>(d_slots + count);
+            hipLaunchKernelGGL(seqset_best_finalize, dim3((unsigned)((count + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, d_slots,
+                               count, d_out);
+            LM_HIP_TRY(hipGetLastError());
+            LM_HIP_TRY(hipMemcpyAsync(best + c0 * records, d_out, count * sizeof(lm_hip_set_best), hipMemcpyDeviceToHost, ctx->stream));
+            return (int)LM_HIP_OK;
+        });
 }

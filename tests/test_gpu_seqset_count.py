@@ -14,7 +14,7 @@ import pytest
 import lightmotif_amd as lm
 from lightmotif_amd.lib import stride as lm_stride
 from lightmotif_amd import _ffi, scan_cli
-from seqset_best_cases import consensus_matrix, edge_records, encode, window_scores
+from seqset_best_cases import best_of, consensus_matrix, edge_records, encode, window_scores
 from seqset_count_cases import count_of, counts_of
 
 pytestmark = pytest.mark.gpu
@@ -227,6 +227,49 @@ def test_short_lane_runs(pli, rows_per_stream):
     finally:
         pli.set_rows_per_stream(0)
     assert np.array_equal(got.counts, want), np.argwhere(got.counts != want)[:5]
+
+
+@pytest.mark.parametrize("protein", [False, True], ids=["dna", "protein"])
+def test_counts_and_best_hits_of_one_walk_agree(pli, protein):
+    """The two reductions of the one record walk (csrc/seqset_walk.hpp) on the same set, at lane runs of the default
+    length, 1 and 7 rows.  Every expectation comes from the host's window scores, neither call predicts the other: at
+    -inf a cell holds the record's non-NaN windows; at the motif's lowest record best a cell is >= 1 exactly where the
+    record has a best hit; just above the motif's highest record best every cell is 0; the best hits are ``best_of``."""
+    k = 21 if protein else 5
+    rng = np.random.default_rng(4_100 + k)
+    records = make_records(rng, 37, k, POOL, 0.0)
+    ms = (1, 4, 17, 36, 40)
+    mats = [make_matrix(rng, m, k, neg_inf_cells=(m == 17)) for m in ms]
+    syms = [symbols_of(r, k) for r in records]
+    scores = [[window_scores(p, s) for s in syms] for p in mats]
+    bests = [[best_of(v) for v in row] for row in scores]
+    found = np.asarray([[b[0] for b in row] for row in bests])
+    assert found.any(axis=1).all() and not found.all()               # every motif fits somewhere, some record is too short
+    cuts = np.zeros((len(ms), 3), dtype=np.float32)
+    for mi, row in enumerate(bests):
+        top = np.asarray([b[2] for b in row if b[0]], dtype=np.float32)
+        cuts[mi] = [-np.inf, top.min(), np.nextafter(top.max(), np.float32(np.inf))]
+    want = counts_of(mats, syms, cuts, window_scores)
+    for mi, row in enumerate(scores):
+        assert want[mi, 0].tolist() == [int(np.count_nonzero(~np.isnan(v))) for v in row]
+        assert np.array_equal(want[mi, 1] >= 1, found[mi]) and not want[mi, 2].any()
+    pssms = [lm.ScoringMatrix(p, protein=protein) for p in mats]
+    seqset = pli.stripe_ascii_set(records, protein=protein, lossy=True)
+    seqset.configure_wrap(max(ms))
+    for rows_per_stream in (0, 1, 7):
+        pli.set_rows_per_stream(rows_per_stream)
+        try:
+            b = pli.scan_best_set(pssms, seqset)
+            c = pli.scan_count_set(pssms, cuts, seqset)
+        finally:
+            pli.set_rows_per_stream(0)
+        assert np.array_equal(c.counts, want), (rows_per_stream, np.argwhere(c.counts != want)[:5])
+        assert np.array_equal(c.counts[:, 1] >= 1, b.found) and not c.counts[:, 2].any(), rows_per_stream
+        assert np.array_equal(b.found, found), rows_per_stream
+        for mi, row in enumerate(bests):
+            for ri, (ok, pos, score) in enumerate(row):
+                if ok:
+                    assert (int(b.position[mi, ri]), np.float32(b.score[mi, ri]).tobytes()) == (pos, score.tobytes()), (rows_per_stream, mi, ri)
 
 
 def test_non_finite_values(pli):

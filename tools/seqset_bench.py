@@ -25,6 +25,13 @@ resident, the calls alone timed) and writes ``profiles/seqset_best_bench.json``:
 ``--count`` measures the hits per (motif, record) on the same set at p = 1e-1 ... 1e-5 (``measure_count``: the list plus a
 ``bincount`` per motif, ``scan_count_set``, and ``scan_best_set`` as the walk's floor) and writes
 ``profiles/seqset_count_bench.json``.
+
+``--best --per-length`` / ``--count --per-length`` time the walk kernels one motif length at a time (``measure_per_length``:
+the same resident set, 8 seeded random motifs of one length M per call, M = 1 ... 36, 40 and 70, medians of ``--runs``)
+and write the series to ``--out``; ``--combine-ab P1 N1 P2 N2`` turns four such files per reduction -- parent, new,
+parent, new, each run with ``LM_HIP_LIBRARY`` pointing at its build -- into ``profiles/seqset_walk_ab.json``: per
+reduction the margin (the largest relative difference between the two parent series at any length) and, per length, the
+ratio of the new medians to the parent's.
 """
 from __future__ import annotations
 
@@ -344,6 +351,77 @@ def main_count(a):
     return 0 if res["answers_equal"] else 1
 
 
+PER_LENGTH_MS = tuple(range(1, 37)) + (40, 70)
+
+
+def measure_per_length(pli, which, n_records=2_000, length=500, n_motifs=8, runs=15, warmup=2):
+    """Median ms of one ``scan_best_set`` / ``scan_count_set`` (one level, about 3 sigma of the random weights) call per
+    motif length on the resident set of the other modes."""
+    from lightmotif_amd.lib import stride as lm_stride
+    _, joined = make_records(n_records, length)
+    offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(length)
+    seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+    seqset.configure_wrap(max(PER_LENGTH_MS))
+    out = {}
+    for m in PER_LENGTH_MS:
+        rng = np.random.default_rng(7_000 + m)
+        mats = []
+        for _ in range(n_motifs):
+            p = np.zeros((m, lm_stride(5, 4)), np.float32)
+            p[:, :5] = rng.normal(0, 2, (m, 5))
+            mats.append(lm.ScoringMatrix(p))
+        batch = pli.prepare_batch(mats)
+        cuts = np.full(n_motifs, 6.0 * np.sqrt(m), dtype=np.float32)
+        call = (lambda: pli.scan_best_set(batch, seqset)) if which == "best" else (lambda: pli.scan_count_set(batch, cuts, seqset))
+        times = []
+        for it in range(warmup + runs):
+            t0 = time.perf_counter()
+            res = call()
+            if it >= warmup:
+                times.append((time.perf_counter() - t0) * 1e3)
+        out[str(m)] = {"median": statistics.median(times), "min": min(times), "max": max(times), "kernel": res.last_kernel}
+    return out
+
+
+def main_per_length(a):
+    which = "best" if a.best else "count"
+    if a.out == str(ROOT / "profiles" / "seqset_bench.json"):
+        raise SystemExit("--per-length: name the series' file with --out (one of the four --combine-ab reads)")
+    res = measure_per_length(lm.Pipeline.hip(0), which, runs=a.runs)
+    Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(a.out).write_text(json.dumps({"tool": f"tools/seqset_bench.py --{which} --per-length", "reduction": which, "runs": a.runs,
+                                       "ms": res}, indent=1) + "\n")
+    print(json.dumps({"reduction": which, "lengths": len(res), "wrote": a.out}))
+    return 0
+
+
+def main_combine_ab(a):
+    """a.combine_ab: per reduction four files, parent, new, parent, new ("best:p1,n1,p2,n2 count:...")."""
+    out = a.out if a.out != str(ROOT / "profiles" / "seqset_bench.json") else str(ROOT / "profiles" / "seqset_walk_ab.json")
+    result = {"tool": "tools/seqset_bench.py --combine-ab", "reductions": {}}
+    ok = True
+    for spec in a.combine_ab:
+        which, _, files = spec.partition(":")
+        files = files.split(",")
+        if which not in ("best", "count") or len(files) != 4:
+            raise SystemExit(f"--combine-ab: `{spec}` is not best:P1,N1,P2,N2 or count:P1,N1,P2,N2")
+        p1, n1, p2, n2 = [json.loads(Path(f).read_text())["ms"] for f in files]
+        med = lambda s, m: s[m]["median"]
+        margin = max(abs(med(p1, m) - med(p2, m)) / min(med(p1, m), med(p2, m)) for m in p1)
+        parent = {m: statistics.median([med(p1, m), med(p2, m)]) for m in p1}
+        new = {m: statistics.median([med(n1, m), med(n2, m)]) for m in p1}
+        ratios = {m: new[m] / parent[m] for m in p1}
+        worst = max(ratios, key=ratios.get)
+        result["reductions"][which] = {"series": {"parent_1": p1, "new_1": n1, "parent_2": p2, "new_2": n2}, "margin": margin,
+                                       "ratio_new_over_parent": ratios, "worst_length": int(worst), "worst_ratio": ratios[worst],
+                                       "within_margin": ratios[worst] <= 1.0 + margin}
+        ok = ok and ratios[worst] <= 1.0 + margin
+        print(json.dumps({"reduction": which, "margin": round(margin, 4), "worst_length": int(worst), "worst_ratio": round(ratios[worst], 4)}))
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps({"within_margin": ok, "wrote": out}))
+    return 0 if ok else 1
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", default="both", choices=["i", "ii", "both"])
@@ -353,7 +431,13 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "seqset_bench.json"))
     ap.add_argument("--best", action="store_true", help="the best hit per record (measure_best) -> profiles/seqset_best_bench.json")
     ap.add_argument("--count", action="store_true", help="hits per (motif, record) (measure_count) -> profiles/seqset_count_bench.json")
+    ap.add_argument("--per-length", action="store_true", help="with --best / --count: one call per motif length (measure_per_length) -> --out")
+    ap.add_argument("--combine-ab", nargs="+", metavar="REDUCTION:P1,N1,P2,N2", help="per-length files of an A/B session -> --out")
     a = ap.parse_args()
+    if a.combine_ab:
+        return main_combine_ab(a)
+    if a.per_length and (a.best or a.count):
+        return main_per_length(a)
     if a.best:
         return main_best(a)
     if a.count:
