@@ -81,14 +81,14 @@ struct ArgmaxRecord {
 //   region              bytes                    holds                                                    users
 //   kPinCounters        [0, 16)                  4 or 8 bytes read back (bad-symbol position, max         layout.hip, handles.hip (ingest), reduce.hip,
 //                                                symbol, hit total), or the {hits, candidates} pair       discrete.hip; score_threshold.hip, scanmax.hip,
-//                                                of a hit list (copied, or written by a kernel)           hits.hip, score_argmax.hip (candidate route)
+//                                                of a hit list (copied, or written by a kernel)           hits.hip, score_argmax_cand.hip
 //   kPinRecord          [0, 64)                  one ArgmaxRecord written by a kernel or a copy; the      reduce.hip, discrete.hip, handles.hip;
-//                                                single-launch argmax raises its generation word          score_argmax.hip (result [0] of kPinArgmaxBatch
-//                                                right behind the record (byte 16)                        at n = 1)
-//   kPinArgmaxBatch     [0, whole)               exact fused argmax: ArgmaxRecord[n], then (64-byte       score_argmax.hip
-//                                                aligned) the FinalizeJob table the finalize kernel
+//                                                single-launch argmax raises its generation word          score_argmax_exact.hip (result [0] of
+//                                                right behind the record (byte 16)                        kPinArgmaxBatch at n = 1)
+//   kPinArgmaxBatch     [0, whole)               exact fused argmax: ArgmaxRecord[n], then (64-byte       score_argmax_exact.hip (layout:
+//                                                aligned) the FinalizeJob table the finalize kernel       argmax_plan.hpp, pinned_jobs_off)
 //                                                reads in place
-//   kPinCandResults     [16, half)               candidate-route argmax: ArgmaxRecord[jobs] behind the    score_argmax.hip
+//   kPinCandResults     [16, half)               candidate-route argmax: ArgmaxRecord[jobs] behind the    score_argmax_cand.hip
 //                                                counters, written by the reduction kernels
 //   kPinScanMaxState    [0, 256)                 Scanner::max window walk: ScanMaxState [0] written by    scanmax.hip
 //                                                the kernels, [1] the initial state staged for upload
@@ -99,7 +99,7 @@ struct ArgmaxRecord {
 //                                                of the records | head of the values, kernel-written
 //   kPinHitReadback     [0, 256 KB)              exact ordering: starts | records | values of a short     hits.hip
 //                                                list in one copy
-//   kPinFoldRecords     [4096, whole)            single-job argmax: one 16-byte record per wavefront      score_argmax.hip
+//   kPinFoldRecords     [4096, whole)            single-job argmax: one 16-byte record per wavefront      score_argmax_exact.hip
 //                                                + the first-cell slot, written by the scoring kernel
 //   kPinU8Out           [4096, half)             the u8 scores of a Scanner block, kernel-written         score_api.hip
 //   kPinUploadHead      [half, whole)            head of the device scratch block, assembled here and     score_plan.hip (upload_head: fused threshold and
@@ -140,7 +140,7 @@ static_assert(kPinHitStaging.end() <= kPinUploadHead.off, "fused threshold: the 
 static_assert(kPinHitReadback.end() <= kPinHitStaging.end(), "the exact ordering's read-back stays inside the staging of the speculative one");
 static_assert(kPinListHead.end() <= kPinUploadHead.off && kPinU8Out.end() <= kPinUploadHead.off, "the lower half's users stay in the lower half");
 // kPinArgmaxBatch and kPinFoldRecords extend past the half mark.  The region they must never meet is kPinUploadHead, whose
-// asynchronous copy may still be reading it; they cannot, because the exact argmax route (launch_score_argmax_exact) and
+// asynchronous copy may still be reading it; they cannot, because the exact argmax route (score_argmax_exact.hip: launch_score_argmax_exact) and
 // the tiled store kernel it may start with never call upload_head, and a call that does synchronises ctx->stream before it
 // returns.  kPinCommBlock (whole block) belongs to calls of comm.hip, which use nothing else of the block.
 
@@ -220,13 +220,13 @@ struct lm_hip_ctx {
     bool list_scan_max = true;   // Scanner::max over a candidate list (scanmax.hip; option "list_scan_max" = 0: always the window walk)
     bool drop_last = true;       // single pair scans of M = 20, 24, ... 36 over M - 1 rows (option "drop_last"; lm_hip_pssm::d_image2_drop)
     bool short_order = true;     // ... short lists of one job counted by the re-scoring kernel, two launches behind it (hits.hip; option "short_order")
-    bool suffix_argmax = true;   // fused argmax of short motifs: try the last rows first (score_argmax.hip)
+    bool suffix_argmax = true;   // fused argmax of short motifs: try the last rows first (score_argmax.hip, argmax_plan.hpp)
     bool multi_motif = true;     // many-motif threshold batches: several motifs of one length per pass
     bool skip_unreachable = true; // fused threshold: no scan when the threshold exceeds the best k-mer's score
     bool tiled = true;           // column counts off the C = 32 / 16 kernels: LDS-tiled kernel (0: one thread per cell)
     size_t count_tile_rows = 0;  // count_symbols (composition.hip): rows per block of the count table, 0 = default (option "count_tile_rows")
     size_t site_chunk = 0;       // windows / count_sites (sites.hip): most sites per chunk, 0 = bounded by the chunk's bytes alone (option "site_chunk")
-    double suffix_occurrences = 0; // fused argmax of short motifs: best k-mers the suffix should hold (0 = ln lambda, score_argmax.hip)
+    double suffix_occurrences = 0; // fused argmax of short motifs: best k-mers the suffix should hold (0 = ln lambda, argmax_plan.hpp)
     int num_cus = 256;
     unsigned long long last_hit_count = 0;  // sizes the next fused-threshold hit list
     unsigned long long last_cand_count = 0; // ... and its candidate list

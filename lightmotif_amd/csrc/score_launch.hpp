@@ -1,4 +1,4 @@
-// score_launch.hpp -- what the launch code of the scoring kernels (score_store.hip, score_argmax.hip, score_threshold.hip,
+// score_launch.hpp -- what the launch code of the scoring kernels (score_store.hip, score_argmax*.hip, score_threshold.hip,
 // scanmax.hip) shares, defined in score_plan.hip: the kernel registry (score_registry.hpp), the stream geometry (plan_c32),
 // and what the fused routes have in common -- the scans of a batch and their launch (ScanPlan, launch_group_scan), stream
 // alternation (BatchStreams), the hit lists' scratch layout and a call's head upload.  Kernel bodies: score_kernels.hpp.
@@ -272,7 +272,15 @@ struct RescoreJob {
 int launch_rescore(lm_hip_ctx *ctx, hipStream_t st, const RescoreJob *d_jobs, const FusedOut &fo, const RescoreJob *host_jobs,
                    size_t n, const ShortOrder *so = nullptr);
 
-// ---- reductions of block records (score_argmax.hip, score_store.hip) ------------------------------------------
+// ---- the routes of the fused argmax (entry points: score_argmax.hip) ------------------------------------------
+
+// score_argmax_exact.hip: every job through the exact kernels, delivered in the form argmax_plan.hpp picks
+int launch_score_argmax_exact(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n, int first_cell_rule, ArgmaxRecord *out);
+// score_argmax_cand.hip: tries the candidate route for the jobs that qualify; done[i] = 1 and out[i] filled for the ones it
+// settled.  Anything else (small jobs, odd shapes, no prefilter, all -inf samples, list overflow) is left for the exact kernel.
+int argmax_by_prefilter(lm_hip_ctx *ctx, const ScoreArgs *jobs, size_t n, ArgmaxRecord *out, char *done);
+
+// ---- reductions of block records (score_argmax_exact.hip, score_store.hip) ------------------------------------
 
 int ensure_ticket(lm_hip_ctx *ctx);  // the "last workgroup folds" counter of the single-launch argmax forms
 

@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "argmax_plan.hpp"  // discrete_threshold: the one map from an f32 threshold to the prefilter's 16-bit one
 #include "score_launch.hpp"
 
 namespace lm {
@@ -348,10 +349,9 @@ int launch_score_threshold_batch(lm_hip_ctx *ctx, const ScoreArgs *jobs, const f
         if (ctx->skip_unreachable && a.pssm->has_prefilter && a.pssm->m >= 1 && ts[i] > best_kmer_score(a.pssm))
             return (int)KIND_SKIP;
         if (a.pssm->has_prefilter && ctx->use_prefilter && std::isfinite(ts[i])) {
-            const double scaled = std::floor(((double)ts[i] - a.pssm->pre_offset) / a.pssm->pre_factor) -
-                                  std::ceil(a.pssm->pre_emax / a.pssm->pre_factor) - 1.0;
-            if (scaled >= 1.0) {
-                tds[i] = scaled > 65535.0 ? 65535u : (unsigned)scaled;
+            const unsigned td = argmax::discrete_threshold((double)ts[i], a.pssm->pre_offset, a.pssm->pre_factor, a.pssm->pre_emax);
+            if (td) {
+                tds[i] = td;
                 if (ctx->pair_prefilter && plan_c32(ctx, a, false, 2).ok)
                     return (int)KIND_PREFILTER2;  // DNA: two symbols per lookup
                 if (plan_c32(ctx, a, false, 1).ok)

@@ -209,11 +209,11 @@ def discrete_weights(pssm, k):
 # ---- the candidate route of the fused argmax: planted +inf windows its sample misses ------------------------------
 
 PLANT_M, PLANT_LENGTH, PLANT_COLS = 13, 101_000_000, 32
-SAMPLE_ROWS = 8   # score_argmax.hip: kSampleRows (one row per half-wave of a 256-thread block)
+SAMPLE_ROWS = 8   # argmax_plan.hpp: kSampleRows (one row per half-wave of a 256-thread block)
 
 
 def sampled_rows(rows, num_cus=256):
-    """Rows the candidate route's sample scores for a lone job (score_argmax.hip, argmax_by_prefilter: chunks of
+    """Rows the candidate route's sample scores for a lone job (argmax_plan.hpp, sample_geometry, restated here: chunks of
     SAMPLE_ROWS rows spread evenly, about 1/1024 of the rows, at most 8 per CU)."""
     nchunks = min(max(rows // 1024 // SAMPLE_ROWS, 32), num_cus * 8)
     stride = (rows - SAMPLE_ROWS) // (nchunks - 1)

@@ -419,6 +419,41 @@ def test_forty_thousand_motifs():
           f"{hits.total} hits")
 
 
+def test_argmax_batch_both_sides_of_the_pinned_job_table():
+    """scan_argmax_batch with 65 536 and with 65 537 jobs: the two sides of the edge at which the exact route's job table
+    (16 bytes of result + 48 bytes of FinalizeJob per job, 64 n <= 4 194 304 = the pinned block; argmax_plan.hpp:
+    exact_zero_copy, asserted at this figure by tests/cpp/test_argmax_plan.cpp) no longer fits the pinned block, so that
+    table and results travel by staged copies through the device scratch instead of being read and written in place.
+    The jobs cycle over 40 matrices of lengths 1 ... 36 on a 2 011 bp sequence (63 rows: far below the suffix and candidate
+    routes); each matrix's best k-mer is planted at a place of its own, so that the answers differ, and one matrix has a
+    NaN weight under the sequence's first window, so that the first-cell rule (pli/mod.rs:142-146) passes through both
+    deliveries.  The oracle scores each matrix once."""
+    rng = np.random.default_rng(65_537)
+    lengths = list(range(1, 37)) + [4, 8, 20, 33]
+    enc = make_enc(rng, 2_011, 5)
+    mats = [make_matrix(rng, m, 5) for m in lengths]
+    for i, p in enumerate(mats):   # the plant: 50 positions apart, the longest motif has 36 rows
+        enc[3 + 50 * i:3 + 50 * i + p.shape[0]] = np.argmax(p[:, :4], axis=1)
+    mats[11][0, enc[0]] = np.nan   # (M = 12) scores[0][0] is NaN: the answer is cell (0, 0), whatever else the matrix scores
+    case = Case(enc, 5, 32, mats)
+    assert np.isnan(case.wants[11][0, 0]) and co.argmax(case.wants[11], 32) == (0, 0)
+    wants = [co.argmax(w, 32) for w in case.wants]
+    assert len({wa for wa in wants}) >= 35   # the plants took: (nearly) every matrix has a cell of its own
+    pli = pipeline({})
+    seq = case.seq(pli)
+    for n in (65_536, 65_537):
+        pssms = [case.pssms[j % len(mats)] for j in range(n)]
+        t0 = time.perf_counter()
+        am = pli.scan_argmax_batch(pssms, seq)
+        dt = time.perf_counter() - t0
+        assert len(am) == n
+        for j in range(n):
+            i = j % len(mats)
+            assert am[j] is not None and am[j][0] == wants[i], (n, j, lengths[i], am[j], wants[i])
+            assert same(am[j][1], case.wants[i][wants[i]]), (n, j, lengths[i], am[j])
+        print(f"scan_argmax_batch, {n} jobs over {len(mats)} matrices: {dt:.3f} s")
+
+
 # ---- g. seeded mixed-batch fuzz -------------------------------------------------------------------------------------
 
 MIX_SEEDS = range(int(os.environ.get("LM_FUZZ_BATCH_MIX_FIRST", "0")), int(os.environ.get("LM_FUZZ_BATCH_MIX_LAST", "60")))

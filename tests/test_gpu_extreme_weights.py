@@ -310,7 +310,7 @@ SUFFIX = [(r, v) for r, v in xw.REGIMES if r in ("overflow_inf", "near_overflow"
 @pytest.mark.parametrize("regime,variant", SUFFIX, ids=[xw.regime_id(r, v) for r, v in SUFFIX])
 def test_suffix_argmax(regime, variant):
     """DNA M = 8 over 2.2 Mbp: the best k-mer is expected ~32 times, so the fused argmax scans only a suffix of the
-    rows at t = B (score_argmax.hip, argmax_by_suffix) when B is finite and the prefilter is sound."""
+    rows at t = B (score_argmax.hip: argmax_by_suffix, by argmax_plan.hpp: suffix_choice) when B is finite and the prefilter is sound."""
     k, m, cols = 5, 8, 32
     pssm_np = xw.make_pssm(regime, variant, m, k)
     enc = xw.make_sequence(regime, variant, 2_200_000, k, m)

@@ -68,6 +68,12 @@ def instructions(elf: Path, names: set[str]) -> dict[str, list[str]]:
         # the numeric form of a branch offset sits before its <symbol+offset>; drop it, the label says it all
         text = re.sub(r"\b\d+\s+(L\d+)$", r"\1", text)
         out[cur].append(re.sub(r"\s+", " ", text))
+    # What follows a kernel's last instruction is the code object's fill up to the next symbol or, behind the LAST kernel of a
+    # translation unit, to the end of the section (`s_nop 0`, and `...` for zero bytes): it changes with the kernel's
+    # neighbours, not with the kernel, so a kernel that moved to another unit would otherwise never compare equal.
+    for text in out.values():
+        while text and text[-1] in ("s_nop 0", "..."):
+            text.pop()
     return out
 
 
