@@ -198,6 +198,9 @@ int lm_hip_ctx_set_track_argmax(lm_hip_ctx *ctx, int enabled);
  * 0 = the default of 1024: a small value makes a small input span many blocks of the table and of its scan),
  * "site_chunk" (most sites per chunk of lm_hip_seqset_windows / lm_hip_seqset_count_sites, 0 = the default: a small value
  * makes a small list cross chunk boundaries),
+ * "variant_chunk" (most variants per chunk of lm_hip_seqset_variant_effects / lm_hip_seqset_variant_hits, 0 = the default of
+ * 2^20: a small value makes a small list cross chunk boundaries), "variant_lds_bytes" (LDS for the tables of one motif group
+ * of those calls, 0 = the default of 24 576: a small value sends small motifs to the kernel that reads global memory),
  * "tally_launches" (1 = count the registry rows launched, lm_hip_ctx_launch_tally), "track_fold_cells" (score_into on handles
  * stores + tracks the maximum in ONE launch below this many cells and with block maxima + two reduction launches from it on;
  * default 8 Mi, 0 = always the latter: lets a small input take the large inputs' route); "xcd_remap" is accepted and ignored (the remap it selected was removed in round 5).  Unknown names:
@@ -624,6 +627,66 @@ int lm_hip_seqset_windows(lm_hip_ctx *ctx, const lm_hip_seqset *set, const size_
 int lm_hip_seqset_count_sites(lm_hip_ctx *ctx, const lm_hip_seqset *set, const size_t *counts, const size_t *widths,
                               const int64_t *shifts, size_t n, const void *sites, size_t site_stride_bytes,
                               uint64_t *tables, size_t capacity, uint64_t *used /* n entries, may be NULL */);
+
+/* What a single-symbol substitution does to the sites of every motif (csrc/variants.hip): does it create, destroy,
+ * strengthen or weaken one?  The reference has no such call; the scores are its ScoringMatrix::score_position
+ * (pwm/mod.rs:651-662) of the record and of the record with one symbol replaced.
+ *   variants    (record r, position p inside the record, alt symbol a), `a` a symbol index, not ASCII.  VALID when
+ *               r < records, p < L_r and a < k, evaluated on 64-bit values without wrap-around.  An invalid variant is not an
+ *               error: every motif reports "none" on both sides for it and its ref_symbol reads 0xFF.
+ *   windows     for motif i (M rows) the starts s = max(0, p - M + 1) ... min(p, L_r - M): all windows that lie inside the
+ *               record and cover p; none when L_r < M
+ *   ref side    the greatest window score under f32 `>`, each score M sequential f32 adds from +0.0 in row order
+ *               (pli/mod.rs:96-105), bit for bit what lm_hip_scan_threshold_seqset reports for that window.  NaN windows
+ *               never compete, -inf windows do, and among equal scores the LOWEST start wins (the rule of
+ *               lm_hip_scan_best_seqset)
+ *   alt side    the same rule over the same starts with the symbol at p replaced by a.  a equal to the resident symbol
+ *               gives the ref side again, bit for bit; a = k - 1 (N / X) is an ordinary symbol
+ *   effect      per side `score` and `back` = p - s (0 ... M - 1); with no window, or only NaN windows, score is a NaN and
+ *               back = LM_HIP_VARIANT_NONE
+ * Wrap rows are never read: the results are the same before and after lm_hip_seqset_configure_wrap and there is no
+ * LM_HIP_ERR_WRAP case.  Both strands are obtained as everywhere else: pass reverse-complemented matrices as further
+ * motifs.  Indels and multi-symbol substitutions are out of scope.
+ * lm_hip_seqset_variant_effects writes the dense block effects[i * n_variants + v] (motif-major, n * n_variants entries of
+ * the caller's memory) and, when ref_symbols is not NULL, the resident symbol of every variant (n_variants bytes).
+ * lm_hip_seqset_variant_hits keeps, per motif i in caller order, the pairs with ref_score >= thresholds[i] or
+ * alt_score >= thresholds[i] under f32 comparison -- a site on at least one allele; a none side never passes, a NaN
+ * threshold keeps nothing, -inf keeps every pair with a non-NaN side.  The list is ordered by motif, then ascending variant
+ * index; counts[i] entries belong to motif i; *hits (release with lm_hip_free; NULL when there are none) holds sum(counts)
+ * entries that equal the dense form's cells bit for bit.  The dense block exists on the device alone, chunk by chunk, and is
+ * compacted there in order: only kept entries cross to the host.
+ * Both calls are deterministic and repeat byte for byte, enqueue on the context's stream and synchronise it, and keep the
+ * caller's variant order (duplicates and unsorted input are fine).  lm_hip_ctx_last_kernel names "variant_effects" (the
+ * tables of a group of motifs staged in LDS) or "variant_effects_global" (a motif whose table exceeds the LDS budget, read
+ * from global memory) -- whichever ran last -- or "variant_gather" when no motif has a window anywhere.
+ * LM_HIP_ERR_BAD_ARGS, before any device work and with a message: a null ctx or set (also when n == 0); with n > 0 a null
+ * `pssms`, null outputs or `thresholds`; with n_variants > 0 a null `variants`; a matrix whose alphabet size differs from
+ * the set's; a set on another device than the context.  LM_HIP_ERR_CAPACITY, before any launch, for a motif of 2^32 rows or
+ * more.  n == 0 or n_variants == 0: LM_HIP_OK, nothing launched, counts zeroed and *hits = NULL.
+ * TEMPORARY DEVICE MEMORY, from the context's scratch (handed back above 2 GB like every other call's): variants are
+ * processed in chunks (option "variant_chunk") and motifs in batches so that one dense block stays within 256 MB, plus
+ * 2 W + 32 bytes per variant of a chunk (W = the longest motif that fits a record); LM_HIP_ERR_OOM when one chunk cannot
+ * be held. */
+typedef struct lm_hip_variant {
+    size_t record;
+    size_t position;
+    uint8_t alt;
+} lm_hip_variant; /* 24 bytes */
+typedef struct lm_hip_variant_effect {
+    float ref_score, alt_score;
+    uint32_t ref_back, alt_back;
+} lm_hip_variant_effect; /* 16 bytes */
+typedef struct lm_hip_variant_hit {
+    uint64_t variant;
+    lm_hip_variant_effect effect;
+} lm_hip_variant_hit; /* 24 bytes */
+#define LM_HIP_VARIANT_NONE 0xFFFFFFFFu
+int lm_hip_seqset_variant_effects(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set,
+                                  const lm_hip_variant *variants, size_t n_variants, lm_hip_variant_effect *effects,
+                                  uint8_t *ref_symbols /* n_variants, may be NULL */);
+int lm_hip_seqset_variant_hits(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds, size_t n,
+                               const lm_hip_seqset *set, const lm_hip_variant *variants, size_t n_variants, size_t *counts,
+                               lm_hip_variant_hit **hits, uint8_t *ref_symbols /* n_variants, may be NULL */);
 
 /* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
  * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the

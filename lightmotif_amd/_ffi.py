@@ -31,6 +31,21 @@ class SetBest(C.Structure):
     _fields_ = [("position", C.c_uint64), ("score", C.c_float), ("found", C.c_int32)]
 
 
+class Variant(C.Structure):
+    _fields_ = [("record", C.c_size_t), ("position", C.c_size_t), ("alt", C.c_uint8)]
+
+
+class VariantEffect(C.Structure):
+    _fields_ = [("ref_score", C.c_float), ("alt_score", C.c_float), ("ref_back", C.c_uint32), ("alt_back", C.c_uint32)]
+
+
+class VariantHit(C.Structure):
+    _fields_ = [("variant", C.c_uint64), ("effect", VariantEffect)]
+
+
+VARIANT_NONE = 0xFFFFFFFF   # LM_HIP_VARIANT_NONE
+
+
 class RegistryRow(C.Structure):
     _fields_ = [("family", C.c_int), ("wide", C.c_int), ("m", C.c_int), ("slot", C.c_int), ("value", C.c_ulonglong)]
 
@@ -132,6 +147,8 @@ SIGNATURES = {
     "lm_hip_seqset_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_windows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "lm_hip_seqset_count_sites": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
+    "lm_hip_seqset_variant_effects": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _vp, _sz, _vp, _vp]),
+    "lm_hip_seqset_variant_hits": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), _vp]),
     "lm_hip_dists_create": (C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     "lm_hip_dists_len": (_sz, [_vp]),
     "lm_hip_dists_info": (C.c_int, [_vp, _sz, _szp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _szp]),

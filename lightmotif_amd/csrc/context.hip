@@ -355,7 +355,7 @@ int lm_hip_device_clock_mhz(int device, unsigned window_us, double *mhz)
 static const char *const kOptionNames[] = {"track_argmax", "xlong_store", "host_fold", "speculate_order", "suffix_argmax",
                                            "multi_motif", "quad_loads", "skip_unreachable", "pair_prefilter",
                                            "pair_prefilter_protein", "chunked_fused", "chunk_rows", "tiled",
-                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done", "count_tile_rows", "tally_launches", "track_fold_cells", "site_chunk"};
+                                           "suffix_occurrences", "prefilter", "sort_hits", "short_order", "time_scan", "drop_last", "block_prefilter", "list_scan_max", "poll_done", "count_tile_rows", "tally_launches", "track_fold_cells", "site_chunk", "variant_chunk", "variant_lds_bytes"};
 
 static int set_option(lm_hip_ctx *ctx, const char *name, double value)
 {
@@ -394,6 +394,14 @@ static int set_option(lm_hip_ctx *ctx, const char *name, double value)
         if (!(value >= 0) || !(value <= 4294967296.0))
             return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: site_chunk must be 0 ... 2^32");
         ctx->site_chunk = (size_t)value;
+    } else if (n == "variant_chunk") {  // most variants per chunk of lm_hip_seqset_variant_effects / _hits (variants.hip); 0 = the default
+        if (!(value >= 0) || !(value <= 4294967296.0))
+            return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: variant_chunk must be 0 ... 2^32");
+        ctx->variant_chunk = (size_t)value;
+    } else if (n == "variant_lds_bytes") {  // LDS for the tables of one motif group of those calls; 0 = the default
+        if (!(value >= 0) || !(value <= 24576.0))
+            return fail(LM_HIP_ERR_BAD_ARGS, "ctx_set_option: variant_lds_bytes must be 0 ... 24576");
+        ctx->variant_lds_bytes = (size_t)value;
     } else if (n == "tally_launches") {  // 1 = count the registry rows launched (lm_hip_ctx_launch_tally)
         ctx->tally_launches = on;
         ctx->tally.clear();

@@ -226,6 +226,8 @@ struct lm_hip_ctx {
     bool tiled = true;           // column counts off the C = 32 / 16 kernels: LDS-tiled kernel (0: one thread per cell)
     size_t count_tile_rows = 0;  // count_symbols (composition.hip): rows per block of the count table, 0 = default (option "count_tile_rows")
     size_t site_chunk = 0;       // windows / count_sites (sites.hip): most sites per chunk, 0 = bounded by the chunk's bytes alone (option "site_chunk")
+    size_t variant_chunk = 0;    // variant_effects / variant_hits (variants.hip): most variants per chunk, 0 = default (option "variant_chunk")
+    size_t variant_lds_bytes = 0; // ... LDS for the tables of one motif group, 0 = default (option "variant_lds_bytes")
     double suffix_occurrences = 0; // fused argmax of short motifs: best k-mers the suffix should hold (0 = ln lambda, argmax_plan.hpp)
     int num_cus = 256;
     unsigned long long last_hit_count = 0;  // sizes the next fused-threshold hit list

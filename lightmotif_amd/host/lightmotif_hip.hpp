@@ -311,9 +311,76 @@ public:
             return EncodedSequence<A>(std::vector<uint8_t>());
         return EncodedSequence<A>(std::move(windows({{Site{r, 0}}}, {n})[0].symbols));
     }
+    // What single-symbol substitutions do to the sites of every motif (csrc/variants.hip).  A variant replaces the symbol at
+    // `position` of `record` by the symbol INDEX `alt`; per (motif, variant) both alleles report the best window that covers
+    // the position and lies inside the record -- the greatest score, NaN windows never competing, the lowest start among
+    // equals -- as score and back = position - start; LM_HIP_VARIANT_NONE and a NaN where there is none.  An invalid variant
+    // (no such record, a position outside it, no such symbol) is not an error: none for every motif, ref_symbol 0xFF.
+    using Variant = lm_hip_variant;
+    using VariantEffect = lm_hip_variant_effect;
+    // effects[i][v] for motif i and variant v; ref_symbols[v]
+    struct VariantEffects {
+        std::vector<std::vector<VariantEffect>> effects;
+        std::vector<uint8_t> ref_symbols;
+    };
+    VariantEffects variant_effects(const std::vector<const ScoringMatrix<A> *> &pssms, const std::vector<Variant> &variants) const
+    {
+        const size_t n = pssms.size(), nv = variants.size();
+        const std::vector<const lm_hip_pssm *> handles = device_handles(pssms);
+        std::vector<VariantEffect> flat(n * nv + 1);
+        VariantEffects out;
+        out.ref_symbols.assign(nv + 1, 0xFF);
+        check(lm_hip_seqset_variant_effects(ctx_->ctx, handles.data(), n, h_, variants.data(), nv, flat.data(), out.ref_symbols.data()));
+        out.ref_symbols.resize(nv);
+        for (size_t i = 0; i < n; ++i)
+            out.effects.emplace_back(flat.begin() + i * nv, flat.begin() + (i + 1) * nv);
+        return out;
+    }
+    // per motif the (variant index, effect) pairs with ref_score >= thresholds[i] or alt_score >= thresholds[i] in f32, ascending
+    // in the variant's index: the dense block never leaves the device
+    struct VariantHit {
+        size_t variant;
+        VariantEffect effect;
+    };
+    struct VariantHits {
+        std::vector<std::vector<VariantHit>> hits;
+        std::vector<uint8_t> ref_symbols;
+    };
+    VariantHits variant_hits(const std::vector<const ScoringMatrix<A> *> &pssms, const std::vector<float> &thresholds,
+                             const std::vector<Variant> &variants) const
+    {
+        const size_t n = pssms.size(), nv = variants.size();
+        if (thresholds.size() != n)
+            throw std::invalid_argument("one threshold per motif");
+        const std::vector<const lm_hip_pssm *> handles = device_handles(pssms);
+        std::vector<size_t> counts(n + 1);
+        lm_hip_variant_hit *h = nullptr;
+        VariantHits out;
+        out.ref_symbols.assign(nv + 1, 0xFF);
+        check(lm_hip_seqset_variant_hits(ctx_->ctx, handles.data(), thresholds.data(), n, h_, variants.data(), nv, counts.data(), &h,
+                                         out.ref_symbols.data()));
+        out.ref_symbols.resize(nv);
+        out.hits.resize(n);
+        size_t pos = 0;
+        for (size_t i = 0; i < n; ++i) {
+            out.hits[i].resize(counts[i]);
+            for (size_t j = 0; j < counts[i]; ++j)
+                out.hits[i][j] = {(size_t)h[pos + j].variant, h[pos + j].effect};
+            pos += counts[i];
+        }
+        lm_hip_free(h);
+        return out;
+    }
     lm_hip_seqset *handle() const { return h_; }
 
 private:
+    std::vector<const lm_hip_pssm *> device_handles(const std::vector<const ScoringMatrix<A> *> &pssms) const
+    {
+        std::vector<const lm_hip_pssm *> handles(pssms.size() + 1, nullptr);  // (never empty: an empty call still hands a pointer over)
+        for (size_t i = 0; i < pssms.size(); ++i)
+            handles[i] = pssms[i]->device(ctx_->ctx);
+        return handles;
+    }
     struct SiteArgs {
         std::vector<size_t> counts;
         std::vector<Site> flat;

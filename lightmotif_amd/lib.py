@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "background_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -412,6 +412,80 @@ class Pipeline:
         lengths = seqset.lengths.reshape(1, -1)
         rows = np.asarray([len(p) for p in batch.pssms], dtype=np.int64).reshape(-1, 1)
         return SetCounts(counts, np.maximum(0, lengths - rows + 1), self.last_kernel if counts.size else "")
+
+    def _variant_args(self, batch: "MotifBatch", seqset: "StripedSequenceSet", records, positions, alts) -> np.ndarray:
+        """The ``lm_hip_variant`` list of a call: records and positions as ``_u64_array`` takes them, ``alts`` symbol indices
+        or a str / bytes of letters (strict table: an unknown letter raises)."""
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        rec, pos = _u64_array(records), _u64_array(positions)
+        if isinstance(alts, (str, bytes, bytearray)):
+            raw = np.frombuffer(alts.encode("latin-1") if isinstance(alts, str) else bytes(alts), dtype=np.uint8)
+            table = np.full(256, 255, dtype=np.uint8)
+            table[np.frombuffer(_symbols(seqset.protein).encode(), dtype=np.uint8)] = np.arange(_k(seqset.protein), dtype=np.uint8)
+            alt = table[raw]
+            if (alt == 255).any():
+                raise InvalidSymbol(f"Invalid symbol: {chr(int(raw[int(np.argmax(alt == 255))]))!r}")
+        else:
+            a = np.asarray(alts)
+            if a.size and a.dtype.kind not in "iu":
+                raise TypeError("alts are symbol indices or letters")
+            alt = np.where((a < 0) | (a > 255), 255, a).astype(np.uint8) if a.size else np.zeros(0, np.uint8)
+        if not rec.shape == pos.shape == alt.shape:
+            raise ValueError(f"{rec.size} records, {pos.size} positions and {alt.size} alts")
+        out = np.zeros(rec.size, dtype=VARIANT_DTYPE)
+        out["record"], out["position"], out["alt"] = rec, pos, alt
+        return out
+
+    def scan_variants_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], seqset: "StripedSequenceSet",
+                          records, positions, alts) -> "SetVariantEffects":
+        """What each single-symbol substitution ``(record, position, alt)`` does to the best window of every motif that
+        covers it (``lm_hip_seqset_variant_effects``): the dense ``(motifs, variants)`` block of both alleles' best scores
+        and window starts.  Windows lie inside the record; NaN windows never compete, the lowest start wins a tie.  An
+        invalid variant (no such record, a position outside it, no such symbol) is not an error: every motif reports
+        none for it."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms)
+        v = self._variant_args(batch, seqset, records, positions, alts)
+        n = len(batch)
+        raw = np.zeros((n, v.size), dtype=VARIANT_EFFECT_DTYPE)
+        ref = np.full(v.size, 255, dtype=np.uint8)
+        spare = np.zeros(2, dtype=np.uint64)      # (an empty block still has to be a pointer)
+        check(self._L.lm_hip_seqset_variant_effects(self._h, batch.handles, n, seqset._h, v.ctypes.data if v.size else None, v.size,
+                                                    raw.ctypes.data if raw.size else spare.ctypes.data,
+                                                    ref.ctypes.data if ref.size else None))
+        if n == 0 and v.size:       # (nothing ran: the resident symbols come from a call of their own)
+            return SetVariantEffects(raw, v, self._variant_symbols(seqset, v), "")
+        return SetVariantEffects(raw, v, ref, self.last_kernel if raw.size else "")
+
+    def _variant_symbols(self, seqset: "StripedSequenceSet", v: np.ndarray) -> np.ndarray:
+        """The resident symbol of every variant, 255 where it is invalid."""
+        k = _k(seqset.protein)
+        sym, ok = seqset._windows(np.array([v.size], dtype=np.uintp), np.array([1], dtype=np.uintp), np.zeros(1, dtype=np.int64),
+                                  np.ascontiguousarray(np.stack([v["record"], v["position"]], axis=1)), 16)
+        return np.where((ok != 0) & (v["alt"] < k), sym, 255).astype(np.uint8)
+
+    def scan_variant_hits_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], thresholds: Optional[Sequence[float]],
+                              seqset: "StripedSequenceSet", records, positions, alts) -> "SetVariantHits":
+        """The sparse form of ``scan_variants_set`` (``lm_hip_seqset_variant_hits``): per motif the (variant, effect) pairs
+        with ``ref_score >= t`` or ``alt_score >= t``, ascending in the variant's index; the dense block never leaves the
+        device.  ``thresholds=None`` takes the batch's."""
+        batch = pssms if isinstance(pssms, MotifBatch) and thresholds is None else \
+            MotifBatch(self, pssms.pssms if isinstance(pssms, MotifBatch) else pssms, thresholds)
+        if len(batch) and batch.thresholds is None:
+            raise ValueError("no thresholds: pass them, or a batch prepared with them")
+        v = self._variant_args(batch, seqset, records, positions, alts)
+        n = len(batch)
+        counts = np.zeros(n, dtype=np.uintp)
+        ref = np.full(v.size, 255, dtype=np.uint8)
+        ptr = C.c_void_p()
+        check(self._L.lm_hip_seqset_variant_hits(self._h, batch.handles, batch.thresholds, n, seqset._h, v.ctypes.data if v.size else None,
+                                                 v.size, counts.ctypes.data if n else None, C.byref(ptr), ref.ctypes.data if ref.size else None))
+        total = int(counts.sum())
+        raw = self._take_array(ptr, total * VARIANT_HIT_DTYPE.itemsize, np.uint8)
+        if n == 0 and v.size:
+            ref = self._variant_symbols(seqset, v)
+        return SetVariantHits(raw.view(VARIANT_HIT_DTYPE) if total else np.zeros(0, dtype=VARIANT_HIT_DTYPE), counts, v, ref,
+                              self.last_kernel if n and v.size else "")
 
     def score_distributions(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"]) -> "ScoreDistributions":
         """The score distributions (pwm/dist.rs:51-226) of a whole motif list, built and kept on the device
@@ -1550,6 +1624,86 @@ class SetCounts:
 
     def __len__(self) -> int:
         return self.counts.shape[0]
+
+
+VARIANT_DTYPE = np.dtype({"names": ["record", "position", "alt"], "formats": [np.uint64, np.uint64, np.uint8],
+                          "offsets": [0, 8, 16], "itemsize": C.sizeof(_ffi.Variant)})   # lm_hip_variant
+VARIANT_EFFECT_DTYPE = np.dtype([("ref_score", np.float32), ("alt_score", np.float32), ("ref_back", np.uint32),
+                                 ("alt_back", np.uint32)])                               # lm_hip_variant_effect
+VARIANT_HIT_DTYPE = np.dtype([("variant", np.uint64), ("effect", VARIANT_EFFECT_DTYPE)])  # lm_hip_variant_hit
+
+
+def _variant_starts(position: np.ndarray, back: np.ndarray) -> np.ndarray:
+    """Record-relative window starts ``position - back``, -1 where ``back`` says none."""
+    none = back == _ffi.VARIANT_NONE
+    return np.where(none, np.int64(-1), (position - np.where(none, 0, back).astype(np.uint64)).astype(np.int64))
+
+
+class SetVariantEffects:
+    """The result of ``Pipeline.scan_variants_set``: ``ref_score`` / ``alt_score`` -- ``(motifs, variants)`` float32, NaN
+    where the allele has no (non-NaN) window -- ``ref_position`` / ``alt_position`` -- int64 record-relative window STARTS,
+    -1 for none, made from ``raw`` when asked for -- ``ref_symbol`` -- ``(variants,)`` uint8, the resident symbol, 255 for an invalid variant -- and ``valid``;
+    ``last_kernel`` names the kernel that ran last for the call ("" when nothing ran)."""
+
+    def __init__(self, raw: np.ndarray, variants: np.ndarray, ref_symbol: np.ndarray, last_kernel: str = ""):
+        self.raw = raw                                   # (motifs, variants) of lm_hip_variant_effect
+        self.ref_score, self.alt_score = raw["ref_score"], raw["alt_score"]
+        self._variants = variants
+        self.ref_symbol = ref_symbol
+        self.valid = ref_symbol != 255
+        self.last_kernel = last_kernel
+
+    @property
+    def ref_position(self) -> np.ndarray:
+        return _variant_starts(self._variants["position"].reshape(1, -1), self.raw["ref_back"])
+
+    @property
+    def alt_position(self) -> np.ndarray:
+        return _variant_starts(self._variants["position"].reshape(1, -1), self.raw["alt_back"])
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return self.raw.shape
+
+    def __len__(self) -> int:
+        return self.raw.shape[0]
+
+
+class SetVariantHits(Sequence):
+    """The result of ``Pipeline.scan_variant_hits_set``: per motif a structured array (``variant`` -- the index into the
+    caller's list -- ``ref_score``, ``alt_score``, ``ref_position``, ``alt_position`` as in ``SetVariantEffects``), cut out
+    of the ONE array of ``lm_hip_variant_hit`` the library returned when an element is asked for (as ``SetHits``);
+    ``counts``, ``total``, ``ref_symbol`` and ``valid`` per variant of the call."""
+
+    DTYPE = np.dtype([("variant", np.int64), ("ref_score", np.float32), ("alt_score", np.float32), ("ref_position", np.int64),
+                      ("alt_position", np.int64)])
+
+    def __init__(self, hits: np.ndarray, counts: np.ndarray, variants: np.ndarray, ref_symbol: np.ndarray, last_kernel: str = ""):
+        self.hits, self.counts, self.variants = hits, counts, variants
+        self.ref_symbol, self.valid, self.last_kernel = ref_symbol, ref_symbol != 255, last_kernel
+        self._starts = np.concatenate(([0], np.cumsum(counts, dtype=np.int64)))
+
+    def __len__(self) -> int:
+        return len(self.counts)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[j] for j in range(*i.indices(len(self)))]
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError(i)
+        h = self.hits[int(self._starts[i]):int(self._starts[i + 1])]
+        out = np.zeros(len(h), dtype=self.DTYPE)
+        position = self.variants["position"][h["variant"].astype(np.int64)]
+        out["variant"], out["ref_score"], out["alt_score"] = h["variant"], h["effect"]["ref_score"], h["effect"]["alt_score"]
+        out["ref_position"] = _variant_starts(position, h["effect"]["ref_back"])
+        out["alt_position"] = _variant_starts(position, h["effect"]["alt_back"])
+        return out
+
+    @property
+    def total(self) -> int:
+        return int(self._starts[-1])
 
 
 class ScoreDistributions:

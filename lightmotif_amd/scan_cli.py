@@ -48,6 +48,15 @@ in all sets (``CountMatrix::from_sequences`` of the ``matched`` strings, pwm/mod
 Both read the windows out of the resident set (``StripedSequenceSet.windows`` / ``count_sites``: one call per set and
 strand; for ``-`` the count table of the reverse matrix's sites is reverse-complemented, pwm/mod.rs:313-321) -- with
 ``--ingest device`` the host never held the text -- and with ``--best`` the best windows are the sites.
+``--variants PATH`` scores single-symbol variants instead of scanning (``Pipeline.scan_variant_hits_set``, one call per set
+and strand).  The file is TSV ``seq_name  pos(1-based)  ref  alt`` with single letters; ``#`` lines and blank lines are
+ignored.  ``-o`` receives one line per (variant, motif, strand) with a site on at least one allele -- the best window that
+covers the position reaches the motif's threshold for ``ref`` or for ``alt`` --
+``seq_index seq_name pos ref alt motif_index motif_name strand ref_pos ref_score alt_pos alt_score``, ordered by sequence,
+then variant in file order, then strand, then motif; ``ref_pos`` / ``alt_pos`` are window starts as the hit table's ``pos``,
+and an allele without a window prints ``.`` for both.  Exit status 2 with a message that names the line: a ``ref`` that is
+not the resident symbol, multi-letter alleles, a non-numeric or zero ``pos`` or one behind the record's end, and, after the
+pass, a ``seq_name`` no record carried.  It excludes ``--best``, ``--counts``, ``--matched`` and ``--site-matrices``.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -233,6 +242,76 @@ def window_text(win: np.ndarray, reverse: bool) -> np.ndarray:
     return letters.view(f"S{win.shape[1]}").reshape(-1).astype(str)
 
 
+class VariantFileError(ValueError):
+    """A line of the ``--variants`` file that cannot be used; the message names it."""
+
+
+def read_variants(handle: TextIO, path: str) -> List[Tuple[int, str, int, int, int]]:
+    """The ``--variants`` file: TSV ``seq_name  pos(1-based)  ref  alt``; ``#`` lines and blank lines are ignored.  Returns
+    ``(line number, seq_name, pos, ref symbol, alt symbol)`` per variant, in file order; ``VariantFileError`` names the line
+    of a multi-letter or unknown allele and of a non-numeric or zero ``pos``."""
+    out = []
+    for number, line in enumerate(handle, 1):
+        text = line.strip()
+        if not text or text.startswith("#"):
+            continue
+        fields = text.split()
+        if len(fields) != 4:
+            raise VariantFileError(f"{path}:{number}: expected `seq_name pos ref alt`, found {len(fields)} fields")
+        name, pos, ref, alt = fields
+        if not pos.isdigit() or int(pos) == 0:
+            raise VariantFileError(f"{path}:{number}: pos `{pos}` is not a 1-based position")
+        symbols = []
+        for what, allele in (("ref", ref), ("alt", alt)):
+            if len(allele) != 1:
+                raise VariantFileError(f"{path}:{number}: {what} `{allele}` is not a single letter (indels and multi-symbol "
+                                       "substitutions are out of scope)")
+            if allele.upper() not in DNA_SYMBOLS:
+                raise VariantFileError(f"{path}:{number}: {what} `{allele}` is not one of {DNA_SYMBOLS}")
+            symbols.append(DNA_SYMBOLS.index(allele.upper()))
+        out.append((number, name, int(pos), symbols[0], symbols[1]))
+    return out
+
+
+def variant_lines(pli: Pipeline, seqset: StripedSequenceSet, names: Sequence[str], first_index: int, by_name: dict, variants: Sequence,
+                  batches: Sequence[Tuple[str, MotifBatch]], motif_names: Sequence[str], path: str, seen: set) -> List[str]:
+    """The ``--variants`` lines of one resident set: every variant whose ``seq_name`` a record of the set carries goes to
+    ``Pipeline.scan_variant_hits_set`` once per strand; lines by record, then variant in file order, then strand, then
+    motif.  ``VariantFileError`` for a ``pos`` behind the record's end and for a ``ref`` that is not the resident symbol."""
+    rec, which = [], []
+    for r, name in enumerate(names):
+        for vi in by_name.get(name, ()):
+            rec.append(r)
+            which.append(vi)
+        if name in by_name:
+            seen.add(name)
+    if not rec:
+        return []
+    lengths = seqset.lengths
+    pos = np.array([variants[vi][2] - 1 for vi in which], dtype=np.int64)
+    alt = np.array([variants[vi][4] for vi in which], dtype=np.uint8)
+    rec = np.array(rec, dtype=np.int64)
+    for j in np.flatnonzero(pos >= lengths[rec]):
+        number, name, p = variants[which[j]][:3]
+        raise VariantFileError(f"{path}:{number}: pos {p} lies behind the end of `{name}` ({int(lengths[rec[j]])} symbols)")
+    found = [(strand, pli.scan_variant_hits_set(batch, None, seqset, rec, pos, alt)) for strand, batch in batches]
+    resident = found[0][1].ref_symbol
+    for j in np.flatnonzero(resident != np.array([variants[vi][3] for vi in which], dtype=np.uint8)):
+        number, name, p, ref = variants[which[j]][:4]
+        raise VariantFileError(f"{path}:{number}: ref `{DNA_SYMBOLS[ref]}` disagrees with `{DNA_SYMBOLS[int(resident[j])]}` at "
+                               f"position {p} of `{name}`")
+    rows = []                                           # (variant of the set, strand, motif, line)
+    for si, (strand, hits) in enumerate(found):
+        for mi in range(len(hits)):
+            for v, rs, as_, rp, ap_ in hits[mi].tolist():
+                _, name, p, ref, a = variants[which[v]]
+                sides = "\t".join(f"{q}\t{_fmt_score(s)}" if q >= 0 else ".\t." for q, s in ((rp, rs), (ap_, as_)))
+                rows.append((v, si, mi, f"{first_index + int(rec[v]) + 1}\t{name}\t{p}\t{DNA_SYMBOLS[ref]}\t{DNA_SYMBOLS[a]}\t{mi + 1}\t"
+                                         f"{motif_names[mi]}\t{strand}\t{sides}\n"))
+    rows.sort(key=lambda row: row[:3])
+    return [row[3] for row in rows]
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
@@ -267,6 +346,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="append a column `matched`: the text of the hit's window, reverse-complemented for strand -")
     ap.add_argument("--site-matrices", metavar="PATH",
                     help="also write a JASPAR-2016 file with, per motif, the count matrix of all its hits' windows")
+    ap.add_argument("--variants", metavar="PATH",
+                    help="score single-symbol variants (TSV: seq_name, 1-based pos, ref, alt) instead of scanning: one line per "
+                         "(variant, motif, strand) with a site on at least one allele")
     return ap
 
 
@@ -297,6 +379,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error("--counts needs a threshold: one of -P, --abs-threshold, --rel-threshold")
         if args.best or args.matched or args.site_matrices:
             ap.error("--counts excludes --best, --matched and --site-matrices")
+    variants = None
+    if args.variants:
+        if args.best or args.counts or args.matched or args.site_matrices:
+            ap.error("--variants excludes --best, --counts, --matched and --site-matrices")
+        try:
+            with _open_text(args.variants) as fh:
+                variants = read_variants(fh, args.variants)
+        except VariantFileError as e:
+            ap.error(str(e))
     pli = Pipeline.hip(args.device)
 
     def sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
@@ -344,6 +435,27 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         strands.append(("-", [p.reverse_complement() for p in direct]))
     max_m = max(lengths, default=0)
     batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
+    if variants is not None:
+        by_name: dict = {}
+        for vi, (_, name, _, _, _) in enumerate(variants):
+            by_name.setdefault(name, []).append(vi)
+        seen: set = set()
+        n_lines = 0
+        with open(args.output, "w") as out:
+            out.write("seq_index\tseq_name\tpos\tref\talt\tmotif_index\tmotif_name\tstrand\tref_pos\tref_score\talt_pos\talt_score\n")
+            try:
+                for first, names, seqset in sets():
+                    lines = variant_lines(pli, seqset, names, first, by_name, variants, batches, [r.id for r in records], args.variants,
+                                          seen)
+                    out.writelines(lines)
+                    n_lines += len(lines)
+            except VariantFileError as e:
+                ap.error(str(e))
+        for number, name, _, _, _ in variants:
+            if name not in seen:
+                ap.error(f"{args.variants}:{number}: no record is called `{name}`")
+        print(f"Wrote {n_lines} lines to {args.output}")
+        return 0
     n_hits = 0
     with contextlib.ExitStack() as files:
         out = files.enter_context(open(args.output, "w"))
