@@ -563,6 +563,44 @@ int lm_hip_scan_best_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, si
 int lm_hip_scan_count_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *thresholds,
                              size_t levels, size_t n, const lm_hip_seqset *set, uint32_t *counts);
 
+/* The total odds of every motif in every record of the set, in ONE call and without a hit list: with the best window
+ * ("max odds") and the hit count ("total hits") the statistic motif-enrichment tools call "sum odds" -- and, over the
+ * number of windows, "average odds" --, the affinity of a record for a factor.  For motif i (M rows, scale s_i) and record
+ * r (L_r symbols)
+ *       sums[i * records + r] = sum over p = 0 .. L_r - M, v_p not NaN, of 2^( fl32(s_i * v_p) )          (a double)
+ *   v_p       the window score exactly as score_into gives it: M sequential f32 adds from +0.0 in row order
+ *             (pli/mod.rs:96-105), bit for bit the score lm_hip_scan_best_seqset and lm_hip_scan_count_seqset see
+ *   scales    n of them, or NULL: all 1.  s_i * v_p is ONE f32 multiply, exact for s_i == 1 (a log2-odds matrix); other
+ *             scales serve matrices in another base (s = log2(base)) or a temperature
+ *   sums      the caller's memory, n * records doubles; every cell is written
+ * Windows that straddle two records or reach the padding never contribute (scan.rs:185-190, per RECORD); NaN windows
+ * contribute nothing, the rule of best and count; -inf windows contribute 0; a +inf window makes the cell +inf.  A record
+ * with no window gives 0.0 and a motif with no window anywhere (no rows, or longer than the sequence) a row of zeros.
+ * The exponential neither overflows nor flushes to zero while the value is a double: x = s * v is split into rint(x) and
+ * an exact f32 fraction in [-1/2, 1/2], the fraction goes through the hardware's f32 exp2 (1 ulp), the result is widened
+ * and scaled by 2^rint(x) in f64 (|x| is clamped at 2 000, where a double is +inf or 0 either way).  A term is therefore
+ * right to about 2^-23 relative, and a cell, a sum of positive terms added in f64, to the same.
+ * Deterministic without a floating-point atomic: a record whose windows lie in one lane's run of the walk is stored by
+ * that lane, the others are merged from per-run partial sums in ascending position order by a second kernel
+ * (csrc/seqset_sum.hip, csrc/seqset_sum_plan.hpp, on the record walk of csrc/seqset_walk.hpp; lm_hip_ctx_last_kernel
+ * names `seqset_sum_fused<M>` up to M = 36, `seqset_sum_generic` beyond).  Calls with the same context settings and the
+ * same list of motifs give bit-identical tables.  The order of the f64 additions follows the cut of the set into lane runs,
+ * so another rows_per_stream (or another number of motifs in the call, which moves the default) may change the last bits of
+ * a cell: by no more than the f64 rounding of the additions, n * 2^-53 relative for n windows.
+ * Measured on one MI355X (tools/seqset_bench.py --sum, profiles/seqset_sum_bench.json; 2 000 records x 500 bp x 8 JASPAR
+ * motifs, the set resident, medians of 15 alternating runs): 0.288 ms against 39.4 ms for lm_hip_scan_threshold_seqset at
+ * -inf plus exp2 and a sum per record on the host, the only way before (137 x); lm_hip_scan_count_seqset at one level, the
+ * same walk with the cheapest reducer, takes 0.127 ms there (sum / count = 2.3 in that alternation, 1.09 in a series of
+ * its own: DESIGN 4.6c.2) and 1.397 against 1.384 ms on 2 000 x 50 000 bp (sum / count = 0.99).  Worst relative
+ * error of a cell against the f64 rule: 6.3e-08.
+ * LM_HIP_ERR_WRAP when the set's wrap < max(M) - 1; LM_HIP_ERR_BAD_ARGS, before any launch, on null arguments (a null
+ * `sums` when n > 0 and the set has records), a matrix whose alphabet size differs from the set's, or a scale that is not
+ * finite or not > 0; LM_HIP_OK with nothing written when n == 0 or the set has no records; LM_HIP_ERR_OOM when the device
+ * cannot hold the cells and partial sums of one motif (motifs are scanned in groups that bound the block at 256 MB).  The
+ * cells are doubles: records of 2^32 symbols and more are served. */
+int lm_hip_scan_sum_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *scales, size_t n,
+                           const lm_hip_seqset *set, double *sums);
+
 /* SymbolCount::count_symbols of a StripedSequence (seq.rs:444-483, the loop of seq.rs:466-482), and the same for every
  * record of a set in ONE call: what Background::from_sequence / from_sequences (abc.rs:404-456) count before
  * Background::from_counts (abc.rs:389-402) turns the table into frequencies, on the resident bytes (csrc/composition.hip).

@@ -1,5 +1,6 @@
 // seqset_walk.hpp -- the record walk the per-record reductions over a resident sequence set share (seqset_best.hip: the
-// best window, seqset_count.hip: the windows that reach a cut-off), and the two kernel bodies that drive it.  The host
+// best window, seqset_count.hip: the windows that reach a cut-off, seqset_sum.hip: the sum of their odds), and the two
+// kernel bodies that drive it.  The host
 // half (kernel table, launcher, entry checks) is seqset_walk_launch.hpp; this file needs no more than kBlock, so that the
 // walk compiles for the host alone as well (tests/cpp/test_seqset_walk.cpp).
 //

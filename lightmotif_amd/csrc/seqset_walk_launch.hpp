@@ -1,5 +1,6 @@
 // seqset_walk_launch.hpp -- the host half of the record walk (seqset_walk.hpp): the table of a route's fused kernels, the
-// rows a lane walks, the launcher and the checks of an entry point, once for seqset_best.hip and seqset_count.hip.
+// rows a lane walks, the launcher and the checks of an entry point, once for seqset_best.hip, seqset_count.hip and
+// seqset_sum.hip.
 //
 // A route describes itself with a struct W: Job (an entry of the job table, { dense, slot_base, ... }), Slot (what the
 // kernels merge into), kName ("seqset_best": the kernels are <kName>_fused<M> and <kName>_generic), kTally (registry family
@@ -54,8 +55,15 @@ static inline unsigned long long walk_rows_per_lane(const lm_hip_ctx *ctx, const
     return std::min<unsigned long long>(std::max<unsigned long long>({4ull * m, cells / lanes, 16ull}), 4096ull);
 }
 
+// Motifs of one group: what launch_walk runs between two copies home (a route whose jobs depend on the group asks too).
+static inline size_t walk_group_size(size_t n, size_t per_job)
+{
+    return std::max<size_t>(1, std::min<size_t>(n, kWalkBlockBytes / std::max<size_t>(per_job, 1)));
+}
+
 // What an entry point checks behind its own null arguments, in `call`'s name (`degenerate`: the motif has no window in
-// the set; `cell_bytes` per (motif, record); `levels`: 0 where the call has none).  *run: there is something to launch.
+// the set; `cell_bytes` per (motif, record); `levels`: 0 where the call has none; `limit`: what 32 bits of a record's
+// length bound in this route, null where nothing does).  *run: there is something to launch.
 static inline int check_walk_call(const char *call, const lm_hip_pssm *const *pssms, size_t n, const lm_hip_seqset *set, const void *result,
                                   size_t cell_bytes, size_t levels, const char *limit, std::vector<char> &degenerate, bool *run)
 {
@@ -73,7 +81,7 @@ static inline int check_walk_call(const char *call, const lm_hip_pssm *const *ps
     }
     if (n == 0 || records == 0)
         return LM_HIP_OK;
-    if (seq->length >> 32)
+    if (limit && seq->length >> 32)
         for (size_t r = 0; r < records; ++r)
             if ((set->offsets[r + 1] - set->offsets[r]) >> 32)
                 return fail(LM_HIP_ERR_CAPACITY, "%s: record %zu holds %llu symbols, %s 2^32 - 1", call, r,
@@ -102,7 +110,7 @@ int launch_walk(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const char *de
     const size_t records = set->offsets.size() - 1;
     const bool off_lds = records + 1 <= kSetLdsOffsets;
     const size_t off_bytes = off_lds ? (records + 1) * sizeof(unsigned long long) : 0;
-    const size_t group = std::max<size_t>(1, std::min<size_t>(n, kWalkBlockBytes / std::max<size_t>(per_job, 1)));
+    const size_t group = walk_group_size(n, per_job);
     const size_t head = (group * sizeof(Job) + 255) & ~(size_t)255;
     LM_TRY(ctx->scratch.reserve(head + group * per_job));
     char *block = static_cast<char *>(ctx->scratch.ptr);

@@ -1739,6 +1739,25 @@ public:
                 out[i][l].assign(flat.begin() + (i * levels + l) * records, flat.begin() + (i * levels + l + 1) * records);
         return out;
     }
+    // The total odds of every motif in every record of a set in one call, without a hit list (lm_hip_scan_sum_seqset):
+    // out[i][r] is the f64 sum of 2^(scale_i * score) over the windows position + M <= len(record) (scan.rs:185-190) of
+    // record r; NaN windows add nothing.  `scales` is empty (all 1: log2-odds matrices) or holds one finite scale > 0 per motif.
+    std::vector<std::vector<double>> scan_sum(const std::vector<const ScoringMatrix<A> *> &pssms, const SequenceSet<A> &set,
+                                              const std::vector<float> &scales = {}) const
+    {
+        const size_t n = pssms.size(), records = set.records();
+        if (!scales.empty() && scales.size() != n)
+            throw std::invalid_argument("no scales, or one per motif");
+        std::vector<const lm_hip_pssm *> handles(n);
+        for (size_t i = 0; i < n; ++i)
+            handles[i] = pssms[i]->device(ctx_->ctx);
+        std::vector<double> flat(n * records);
+        check(lm_hip_scan_sum_seqset(ctx_->ctx, handles.data(), scales.empty() ? nullptr : scales.data(), n, set.handle(), flat.data()));
+        std::vector<std::vector<double>> out(n);
+        for (size_t i = 0; i < n; ++i)
+            out[i].assign(flat.begin() + i * records, flat.begin() + (i + 1) * records);
+        return out;
+    }
 
     // ---- row-sharded jobs across the GPUs of a node -----------------------------------
     // Score::score_rows_into takes a row range so that a sequence can be cut (pli/mod.rs:72-78):

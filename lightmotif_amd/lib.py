@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "SetSums", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "background_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -412,6 +412,29 @@ class Pipeline:
         lengths = seqset.lengths.reshape(1, -1)
         rows = np.asarray([len(p) for p in batch.pssms], dtype=np.int64).reshape(-1, 1)
         return SetCounts(counts, np.maximum(0, lengths - rows + 1), self.last_kernel if counts.size else "")
+
+    def scan_sum_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], seqset: "StripedSequenceSet", scale=None) -> "SetSums":
+        """The total odds of every motif in every record, in one call and without a hit list (``lm_hip_scan_sum_seqset``):
+        per (motif, record) the f64 sum of ``2 ** (scale * score)`` over the windows ``position + M <= len(record)``
+        (scan.rs:185-190); NaN windows add nothing.  ``scale`` is None (1: log2-odds matrices), one number or one per motif,
+        finite and > 0 (``log2(base)`` for a matrix in another base, or a temperature).  Of a ``MotifBatch`` only the
+        handles are used."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms)
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        n, records = len(batch), len(seqset)
+        scales = None
+        if scale is not None:
+            scales = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32), (n,)) if np.ndim(scale) == 0 else scale,
+                                          dtype=np.float32)
+            if scales.shape != (n,):
+                raise ValueError("scale: one number, or one per motif")
+        sums = np.zeros((n, records), dtype=np.float64)
+        check(self._L.lm_hip_scan_sum_seqset(self._h, batch.handles, scales.ctypes.data_as(C.POINTER(C.c_float)) if scales is not None else None,
+                                             n, seqset._h, sums.ctypes.data_as(C.POINTER(C.c_double)) if sums.size else None))
+        lengths = seqset.lengths.reshape(1, -1)
+        rows = np.asarray([len(p) for p in batch.pssms], dtype=np.int64).reshape(-1, 1)
+        return SetSums(sums, np.maximum(0, lengths - rows + 1), self.last_kernel if sums.size else "")
 
     def _variant_args(self, batch: "MotifBatch", seqset: "StripedSequenceSet", records, positions, alts) -> np.ndarray:
         """The ``lm_hip_variant`` list of a call: records and positions as ``_u64_array`` takes them, ``alts`` symbol indices
@@ -1624,6 +1647,32 @@ class SetCounts:
 
     def __len__(self) -> int:
         return self.counts.shape[0]
+
+
+class SetSums:
+    """The result of ``Pipeline.scan_sum_set``: ``sums`` -- ``(motifs, records)`` float64, the total odds of a motif in a
+    record -- and ``windows`` -- ``(motifs, records)`` int64, the windows there are, ``max(0, L_r - M_i + 1)``, made on
+    the host from the record lengths; ``last_kernel`` names the kernel that ran last for the call ("" when nothing ran)."""
+
+    def __init__(self, sums: np.ndarray, windows: np.ndarray, last_kernel: str = ""):
+        self.sums, self.windows, self.last_kernel = sums, windows, last_kernel
+
+    @property
+    def shape(self) -> Tuple[int, int]:
+        return self.sums.shape
+
+    def __len__(self) -> int:
+        return self.sums.shape[0]
+
+    def mean(self) -> np.ndarray:
+        """The average odds per window, NaN where a record has no window."""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(self.windows > 0, self.sums / np.maximum(self.windows, 1), np.nan)
+
+    def log2(self) -> np.ndarray:
+        """log2 of the total odds: -inf where the sum is 0."""
+        with np.errstate(divide="ignore"):
+            return np.log2(self.sums)
 
 
 VARIANT_DTYPE = np.dtype({"names": ["record", "position", "alt"], "formats": [np.uint64, np.uint64, np.uint8],

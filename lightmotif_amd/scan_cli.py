@@ -31,6 +31,11 @@ play no part.
 window, ``seq_index seq_name motif_index motif_name strand windows hits`` -- the windows of the motif in that record and
 how many of them reach the motif's threshold (``Pipeline.scan_count_set``: no hit list is made).  It needs one of ``-P``,
 ``--abs-threshold``, ``--rel-threshold`` and excludes ``--best``, ``--matched`` and ``--site-matrices``.
+``--sum-odds`` writes, instead of hits, the total affinity: ONE line per (sequence, strand, motif) that has a window,
+``seq_index seq_name motif_index motif_name strand windows sum_odds log2_mean_odds`` -- the windows of the motif in that
+record, the sum of ``2 ** score`` over them (``Pipeline.scan_sum_set``: no hit list is made; the scores are log2 odds) and
+``log2(sum_odds / windows)``, both written with ``repr``.  Thresholds play no part; it excludes ``--best``, ``--counts``,
+``--variants``, ``--matched`` and ``--site-matrices``.
 ``--pvalues device`` (the default) builds the score distributions of all motifs on the device
 (``Pipeline.score_distributions``): the thresholds of ``-P`` come from one call, and the ``pvalue`` column of a set from one
 call per strand on the set's hits.  ``--pvalues host`` is the per-motif, per-hit host code of ``dist.py``; the TSV is the
@@ -65,6 +70,7 @@ from __future__ import annotations
 import argparse
 import contextlib
 import gzip
+import math
 import sys
 from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
 
@@ -327,6 +333,8 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--counts", action="store_true",
                     help="write the number of hits of every motif in every record instead of the hits (needs -P, "
                          "--abs-threshold or --rel-threshold)")
+    ap.add_argument("--sum-odds", action="store_true",
+                    help="write the sum of 2 ** score over the windows of every motif in every record instead of the hits")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--batch-bases", type=int, default=DEFAULT_BATCH_BASES,
                     help="bases of sequence gathered into one resident set and scanned with one call per strand "
@@ -350,6 +358,12 @@ def build_parser() -> argparse.ArgumentParser:
                     help="score single-symbol variants (TSV: seq_name, 1-based pos, ref, alt) instead of scanning: one line per "
                          "(variant, motif, strand) with a site on at least one allele")
     return ap
+
+
+def log2_mean_odds(total: float, windows: int) -> float:
+    """``log2(total / windows)`` of a ``--sum-odds`` line: -inf for a total of 0, +inf for one of +inf."""
+    mean = total / windows
+    return math.log2(mean) if 0.0 < mean < math.inf else (-math.inf if mean == 0.0 else mean)
 
 
 def hit_pvalues(dists, motif: np.ndarray, score: np.ndarray) -> np.ndarray:
@@ -379,6 +393,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error("--counts needs a threshold: one of -P, --abs-threshold, --rel-threshold")
         if args.best or args.matched or args.site_matrices:
             ap.error("--counts excludes --best, --matched and --site-matrices")
+    if args.sum_odds and (args.best or args.counts or args.variants or args.matched or args.site_matrices):
+        ap.error("--sum-odds excludes --best, --counts, --variants, --matched and --site-matrices")
     variants = None
     if args.variants:
         if args.best or args.counts or args.matched or args.site_matrices:
@@ -461,6 +477,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         out = files.enter_context(open(args.output, "w"))
         if args.counts:
             out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tstrand\twindows\thits\n")
+        elif args.sum_odds:
+            out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tstrand\twindows\tsum_odds\tlog2_mean_odds\n")
         else:
             out.write("seq_index\tseq_name\tmotif_index\tmotif_name\tpos\tstrand\tscore\tpvalue" + ("\tmatched" if args.matched else "") + "\n")
         site_totals = [np.zeros((m, len(DNA_SYMBOLS)), dtype=np.int64) for m in lengths] if args.site_matrices else None
@@ -485,6 +503,22 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
                     for mi, (w, h) in enumerate(zip(windows, hits)):
                         if w > 0:
                             out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{strand}\t{w}\t{h}\n")
+                            wrote += 1
+            return wrote
+
+        def write_sums(first_index: int, names: List[str], seqset: StripedSequenceSet) -> int:
+            seqset.configure_wrap(max_m)                                   # main.rs:543
+            tables = [(strand, pli.scan_sum_set(batch, seqset)) for strand, batch in batches]
+            if composition is not None:
+                write_composition(first_index, names, seqset)
+            wrote = 0
+            for r, name in enumerate(names):
+                for strand, res in tables:
+                    windows, sums = res.windows[:, r].tolist(), res.sums[:, r].tolist()
+                    for mi, (w, total) in enumerate(zip(windows, sums)):
+                        if w > 0:
+                            out.write(f"{first_index + r + 1}\t{name}\t{mi + 1}\t{records[mi].id}\t{strand}\t{w}\t{total!r}\t"
+                                      f"{log2_mean_odds(total, w)!r}\n")
                             wrote += 1
             return wrote
 
@@ -522,12 +556,12 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             return wrote
 
         for first, names, seqset in sets():
-            n_hits += (write_counts if args.counts else write_set)(first, names, seqset)
+            n_hits += (write_counts if args.counts else write_sums if args.sum_odds else write_set)(first, names, seqset)
         if site_totals is not None:
             if any(int(t.max(initial=0)) > 0xFFFFFFFF for t in site_totals):
                 raise OverflowError("--site-matrices: a site count exceeds the u32 of a count matrix")
             lmio.write([lmio.Record(r.id, r.description, CountMatrix(t)) for r, t in zip(records, site_totals)], args.site_matrices)
-    print(f"Wrote {n_hits} {'lines' if args.counts else 'hits'} to {args.output}")
+    print(f"Wrote {n_hits} {'lines' if args.counts or args.sum_odds else 'hits'} to {args.output}")
     return 0
 
 

@@ -26,6 +26,11 @@ resident, the calls alone timed) and writes ``profiles/seqset_best_bench.json``:
 ``bincount`` per motif, ``scan_count_set``, and ``scan_best_set`` as the walk's floor) and writes
 ``profiles/seqset_count_bench.json``.
 
+``--sum`` measures the total odds per (motif, record) on the same set (``measure_sum``: the list at -inf plus ``exp2`` and a
+sum per record on the host, ``scan_sum_set``, and ``scan_count_set`` as the walk with the cheapest reducer; then
+``scan_sum_set`` and ``scan_count_set`` on 2 000 records x 50 000 bp, where a record spans many lane runs and the merge of the
+partial sums has work) and writes ``profiles/seqset_sum_bench.json``.
+
 ``--best --per-length`` / ``--count --per-length`` time the walk kernels one motif length at a time (``measure_per_length``:
 the same resident set, 8 seeded random motifs of one length M per call, M = 1 ... 36, 40 and 70, medians of ``--runs``)
 and write the series to ``--out``; ``--combine-ab P1 N1 P2 N2`` turns four such files per reduction -- parent, new,
@@ -351,6 +356,94 @@ def main_count(a):
     return 0 if res["answers_equal"] else 1
 
 
+def host_sums(res, n_records):
+    """Leg A of measure_sum: ``(motifs, records)`` f64 from a ``SetHits`` at -inf -- ``2 ** score`` of every window in f64
+    and one weighted ``bincount`` per motif."""
+    out = np.zeros((len(res), n_records), dtype=np.float64)
+    for mi in range(len(res)):
+        rec, _, val = res[mi]
+        out[mi] = np.bincount(rec, weights=np.exp2(val.astype(np.float64)), minlength=n_records)
+    return out
+
+
+def measure_sum(pli, n_records, length, n_motifs, runs=5, warmup=1, long_length=50_000):
+    """Total odds per (motif, record) on one resident set, three legs, alternating, medians of `runs` after `warmup`:
+
+      A   ``scan_threshold_set`` at -inf + ``np.exp2`` + one weighted ``bincount`` per motif: the only way before
+          ``scan_sum_set`` (a 16-byte hit for every window of every motif);
+      B   ``scan_sum_set``;
+      C   ``scan_count_set`` at one level (p = 1e-3): the same walk with the cheapest reducer, so B / C is the price of the
+          exponential, the f64 add and the merge.
+
+    ``worst_relative_error``: B against A's f64 sums of ``2 ** score`` (the f64 rule; A's own rounding is n * 2^-53).
+    ``long``: B and C on `n_records` records of `long_length` bp (None: skipped), where every record spans many lane runs."""
+    pssms, _ = load_motifs(n_motifs)
+    lengths = [len(p) for p in pssms]
+    max_m = max(lengths)
+    dists = pli.score_distributions(pssms)
+    cuts = dists.thresholds(1e-3)
+    batch = pli.prepare_batch(pssms)
+    everything = pli.prepare_batch(pssms, [-np.inf] * len(pssms))
+    kernels = set()
+
+    def legs(seqset):
+        def way_a():
+            return host_sums(pli.scan_threshold_set(everything, None, seqset), n_records)
+
+        def way_b():
+            res = pli.scan_sum_set(batch, seqset)
+            kernels.add(res.last_kernel)
+            return res.sums
+
+        def way_c():
+            return pli.scan_count_set(batch, cuts, seqset).counts
+        return way_a, way_b, way_c
+
+    _, joined = make_records(n_records, length)
+    offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(length)
+    seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+    seqset.configure_wrap(max_m)
+    way_a, way_b, way_c = legs(seqset)
+    a, b = way_a(), way_b()
+    worst = float(np.max(np.abs(b - a) / a))
+    repeat_equal = way_b().tobytes() == b.tobytes()
+    ms = alternate({"A": way_a, "B": way_b, "C": way_c}, runs, warmup)
+    windows = int(sum(max(0, length - m + 1) for m in lengths)) * n_records
+    out = {"records": n_records, "record_length": length, "motifs": len(pssms), "motif_lengths": lengths, "runs": runs, "warmup": warmup,
+           "windows": windows, "ms": ms, "A_over_B": ms["A"]["median"] / ms["B"]["median"], "B_over_C": ms["B"]["median"] / ms["C"]["median"],
+           "worst_relative_error": worst, "tolerance": 2.0 ** -21, "within_tolerance": worst <= 2.0 ** -21, "repeat_bit_identical": repeat_equal}
+    if long_length:
+        del seqset
+        _, joined = make_records(n_records, long_length)
+        offsets = np.arange(n_records + 1, dtype=np.uint64) * np.uint64(long_length)
+        seqset = pli.stripe_ascii_set(joined, lossy=True, offsets=offsets)
+        seqset.configure_wrap(max_m)
+        _, way_b, way_c = legs(seqset)
+        first = way_b()
+        ms_long = alternate({"B": way_b, "C": way_c}, runs, warmup, untimed_first=())
+        out["long"] = {"records": n_records, "record_length": long_length, "ms": ms_long,
+                       "B_over_C": ms_long["B"]["median"] / ms_long["C"]["median"], "repeat_bit_identical": way_b().tobytes() == first.tobytes(),
+                       "ns_per_window": {k: v["median"] * 1e6 / (sum(max(0, long_length - m + 1) for m in lengths) * n_records)
+                                         for k, v in ms_long.items()}}
+    out["kernel"] = sorted(kernels)
+    return out
+
+
+def main_sum(a):
+    pli = lm.Pipeline.hip(0)
+    res = measure_sum(pli, 2_000, 500, 8, runs=a.runs, warmup=2)
+    out = a.out if a.out != str(ROOT / "profiles" / "seqset_bench.json") else str(ROOT / "profiles" / "seqset_sum_bench.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps({"tool": "tools/seqset_bench.py --sum", "device": "MI355X (gfx950)", "case": res}, indent=1) + "\n")
+    print(json.dumps({"A_ms": round(res["ms"]["A"]["median"], 3), "B_ms": round(res["ms"]["B"]["median"], 3), "C_ms": round(res["ms"]["C"]["median"], 3),
+                      "A_over_B": round(res["A_over_B"], 2), "B_over_C": round(res["B_over_C"], 2), "worst_relative_error": res["worst_relative_error"]}))
+    if "long" in res:
+        print(json.dumps({"long_B_ms": round(res["long"]["ms"]["B"]["median"], 3), "long_C_ms": round(res["long"]["ms"]["C"]["median"], 3),
+                          "long_B_over_C": round(res["long"]["B_over_C"], 2)}))
+    print(json.dumps({"within_tolerance": res["within_tolerance"], "repeat_bit_identical": res["repeat_bit_identical"], "wrote": out}))
+    return 0 if res["within_tolerance"] and res["repeat_bit_identical"] else 1
+
+
 PER_LENGTH_MS = tuple(range(1, 37)) + (40, 70)
 
 
@@ -431,6 +524,7 @@ def main():
     ap.add_argument("--out", default=str(ROOT / "profiles" / "seqset_bench.json"))
     ap.add_argument("--best", action="store_true", help="the best hit per record (measure_best) -> profiles/seqset_best_bench.json")
     ap.add_argument("--count", action="store_true", help="hits per (motif, record) (measure_count) -> profiles/seqset_count_bench.json")
+    ap.add_argument("--sum", action="store_true", help="total odds per (motif, record) (measure_sum) -> profiles/seqset_sum_bench.json")
     ap.add_argument("--per-length", action="store_true", help="with --best / --count: one call per motif length (measure_per_length) -> --out")
     ap.add_argument("--combine-ab", nargs="+", metavar="REDUCTION:P1,N1,P2,N2", help="per-length files of an A/B session -> --out")
     a = ap.parse_args()
@@ -442,6 +536,8 @@ def main():
         return main_best(a)
     if a.count:
         return main_count(a)
+    if a.sum:
+        return main_sum(a)
     pli = lm.Pipeline.hip(0)
     result = {"tool": "tools/seqset_bench.py", "device": "MI355X (gfx950)", "cases": {}}
     for name in (["i", "ii"] if a.case == "both" else [a.case]):
