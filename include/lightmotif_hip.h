@@ -726,6 +726,52 @@ int lm_hip_seqset_variant_hits(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms,
                                const lm_hip_seqset *set, const lm_hip_variant *variants, size_t n_variants, size_t *counts,
                                lm_hip_variant_hit **hits, uint8_t *ref_symbols /* n_variants, may be NULL */);
 
+/* A sequence set cut out of a resident set, on the device (csrc/regions.hip, csrc/regions_plan.hpp): a genome is uploaded
+ * once as a set of contigs, and every peak set, promoter set or variant neighbourhood -- a BED file of intervals -- becomes
+ * a derived set that every set call above takes as it is, without the genome crossing to the host again.  The reference has
+ * no such call; the result is the StripedSequence (seq.rs:288-313) of the extracted records laid end to end.
+ *   regions     n regions in caller order; they may be unsorted, duplicated or overlapping, so the result may be larger
+ *               than its source.  Record i of the result is region i: the result keeps n records and indices stay aligned
+ *               with the caller's table.
+ *   clipping    a region names [start, end) of source record `record` (BED: 0-based, half-open) and is clipped to the
+ *               record: s = max(start, 0), e = min(end, L_record), compared on 64-bit values with no intermediate that can
+ *               wrap.  record >= records, or s >= e after clipping (which includes start >= end), is not an error: the region
+ *               gives an EMPTY record.
+ *   taken       may be NULL; otherwise n entries: taken[i] = (s, e), and s == e == 0 for an empty region
+ *   strand      0: the symbols [s, e) in source order.  1 (DNA sets only): the reverse complement -- symbol j of the record
+ *               is the complement (abc.rs:174-185) of source symbol e - 1 - j, on bytes 0 <-> 2 and 1 <-> 3 (A <-> T,
+ *               C <-> G); every other byte (N, and whatever an adopted matrix may hold) maps to itself.
+ *   out         an ordinary lm_hip_seqset on the source's device, with the source's cols and k, and wrap 0: its matrix
+ *               and offsets equal, byte for byte, what lm_hip_seqset_from_encoded builds from the same records extracted
+ *               on the host
+ *   reads       symbol q of the source's concatenation sits at row q % rows, column q / rows (pli/mod.rs:178-200); wrap
+ *               rows of the source are never read, so the result is the same before and after
+ *               lm_hip_seqset_configure_wrap(src)
+ * LM_HIP_ERR_BAD_ARGS, before any device work and with a message: a null ctx, src or out; null regions with n > 0; a strand
+ * other than 0 or 1; strand == 1 on a set whose alphabet is not DNA (k != 5); a set on another device than the context.
+ * LM_HIP_ERR_CAPACITY when the result would exceed the 2^40 cells a hit list addresses; LM_HIP_ERR_OOM as
+ * lm_hip_seqset_from_encoded.  On any failure *out is NULL.  n == 0: LM_HIP_OK, a set of zero records, nothing launched;
+ * all regions empty: n empty records, nothing launched.  Deterministic: a call repeats byte for byte.  Enqueues on the
+ * context's stream and synchronises it; lm_hip_ctx_last_kernel names "region_gather" afterwards (a lane gathers 16
+ * consecutive bytes of the result's joined text, one byte per source row, and stores them at once; the stripe kernel of
+ * lm_hip_seq_from_encoded then lays the text out).
+ * TEMPORARY DEVICE MEMORY, from the context's scratch (free for the next call when this one returns, and handed back above
+ * 2 GB like every other call's): the joined text of the result (its length) and 24 bytes per non-empty region.
+ * COST: a source record is a column walk of the striped matrix, so every gathered byte reads a 32-byte sector.  That suits
+ * region sets that cover a few percent of the source; a region set that tiles the whole source re-reads it about 32 times
+ * through the cache (tools/regions_bench.py, profiles/regions_bench.json measure both). */
+typedef struct lm_hip_region {
+    size_t record;
+    int64_t start;
+    int64_t end;
+    uint8_t strand;
+} lm_hip_region; /* 32 bytes */
+typedef struct lm_hip_region_span {
+    uint64_t start, end;
+} lm_hip_region_span;
+int lm_hip_seqset_from_regions(lm_hip_ctx *ctx, const lm_hip_seqset *src, const lm_hip_region *regions, size_t n,
+                               lm_hip_seqset **out, lm_hip_region_span *taken /* n entries, may be NULL */);
+
 /* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
  * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the
  * `pvalue` column (main.rs:335), built and queried on the device (csrc/dist.hip) instead of motif by motif, hit by hit on

@@ -46,6 +46,10 @@ class VariantHit(C.Structure):
 VARIANT_NONE = 0xFFFFFFFF   # LM_HIP_VARIANT_NONE
 
 
+class Region(C.Structure):
+    _fields_ = [("record", C.c_size_t), ("start", C.c_int64), ("end", C.c_int64), ("strand", C.c_uint8)]
+
+
 class RegistryRow(C.Structure):
     _fields_ = [("family", C.c_int), ("wide", C.c_int), ("m", C.c_int), ("slot", C.c_int), ("value", C.c_ulonglong)]
 
@@ -150,6 +154,7 @@ SIGNATURES = {
     "lm_hip_seqset_count_sites": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),
     "lm_hip_seqset_variant_effects": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _vp, _sz, _vp, _vp]),
     "lm_hip_seqset_variant_hits": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), _vp]),
+    "lm_hip_seqset_from_regions": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_vp), _vp]),
     "lm_hip_dists_create": (C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     "lm_hip_dists_len": (_sz, [_vp]),
     "lm_hip_dists_info": (C.c_int, [_vp, _sz, _szp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _szp]),

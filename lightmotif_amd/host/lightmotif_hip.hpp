@@ -311,6 +311,18 @@ public:
             return EncodedSequence<A>(std::vector<uint8_t>());
         return EncodedSequence<A>(std::move(windows({{Site{r, 0}}}, {n})[0].symbols));
     }
+    // A set cut out of this one on the device (lm_hip_seqset_from_regions, csrc/regions.hip): record i of the result is
+    // [start, end) of source record `record` (0-based, half-open), clipped to that record, as it stands (strand 0) or as
+    // its reverse complement (strand 1, DNA only).  A region with no such record, or clipped to nothing, is an empty record.
+    // `taken` (may be null) receives, per region, what was cut after clipping; (0, 0) for an empty one.
+    SequenceSet regions(const std::vector<lm_hip_region> &regions, std::vector<lm_hip_region_span> *taken = nullptr) const
+    {
+        if (taken)
+            taken->assign(regions.size(), lm_hip_region_span{0, 0});
+        lm_hip_seqset *h = nullptr;
+        check(lm_hip_seqset_from_regions(ctx_->ctx, h_, regions.data(), regions.size(), &h, taken ? taken->data() : nullptr));
+        return SequenceSet(ctx_, h);
+    }
     // What single-symbol substitutions do to the sites of every motif (csrc/variants.hip).  A variant replaces the symbol at
     // `position` of `record` by the symbol INDEX `alt`; per (motif, variant) both alleles report the best window that covers
     // the position and lies inside the record -- the greatest score, NaN windows never competing, the lowest start among

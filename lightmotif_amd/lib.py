@@ -26,7 +26,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "SetHits", "SetBest", "SetCounts", "SetSums", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "RegionMap", "SetHits", "SetBest", "SetCounts", "SetSums", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "background_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -908,6 +908,76 @@ def _site_args(sites, widths, shifts=0):
     return counts, w, sh, buf, stride_
 
 
+REGION_DTYPE = np.dtype([("record", np.uint64), ("start", np.int64), ("end", np.int64), ("strand", np.uint8)], align=True)
+assert REGION_DTYPE.itemsize == C.sizeof(_ffi.Region) == 32
+
+
+def _strand_array(strands, n: int) -> np.ndarray:
+    """0 / 1 per region from ``None`` (all plus), 0/1, booleans or ``'+'`` / ``'-'`` / ``'.'`` (a dot counts as plus)."""
+    if strands is None:
+        return np.zeros(n, dtype=np.uint8)
+    a = np.asarray(strands)
+    if a.ndim != 1:
+        raise ValueError("strands are one-dimensional")
+    if a.dtype.kind in "US" or a.dtype == object:
+        names = {"+": 0, ".": 0, "-": 1, 0: 0, 1: 1, False: 0, True: 1}
+        out = np.zeros(a.size, dtype=np.uint8)
+        for i, s in enumerate(a.tolist()):
+            s = s.decode("ascii", "replace") if isinstance(s, bytes) else s
+            if s not in names:
+                raise ValueError(f"strand {s!r}: '+', '-', '.', 0 or 1")
+            out[i] = names[s]
+        return out
+    if a.dtype.kind not in "biu" and a.size:
+        raise TypeError("strands: 0/1, booleans or '+' / '-' / '.'")
+    if a.size and ((a != 0) & (a != 1)).any():
+        raise ValueError("a strand is 0 or 1")
+    return a.astype(np.uint8)
+
+
+def _region_args(records, starts, ends, strands=None) -> np.ndarray:
+    """The ``lm_hip_region`` table of ``StripedSequenceSet.regions``; ``ValueError`` when the lengths disagree."""
+    rec = _u64_array(records)
+    s, e = np.asarray(starts), np.asarray(ends)
+    for name, a in (("starts", s), ("ends", e)):
+        if a.size and a.dtype.kind not in "iu":
+            raise TypeError(f"{name} are integers")
+        if a.ndim != 1:
+            raise ValueError(f"{name} are one-dimensional")
+    st = _strand_array(strands, rec.size)
+    if not rec.size == s.size == e.size == st.size:
+        raise ValueError(f"{rec.size} records, {s.size} starts, {e.size} ends and {st.size} strands")
+    reg = np.zeros(rec.size, dtype=REGION_DTYPE)
+    reg["record"], reg["start"], reg["end"], reg["strand"] = rec, s.astype(np.int64), e.astype(np.int64), st
+    return reg
+
+
+class RegionMap:
+    """Where the records of a derived set (``StripedSequenceSet.regions``) came from: ``records`` and ``strands`` as
+    they were asked for and the ``taken`` table the call returned.  Pure numpy; nothing here touches the device."""
+
+    def __init__(self, records, taken, strands=None):
+        self.records = np.asarray(records, dtype=np.int64)
+        self.taken = np.asarray(taken, dtype=np.int64).reshape(-1, 2)
+        self.strands = _strand_array(strands, self.records.size)
+        if not self.records.size == self.taken.shape[0] == self.strands.size:
+            raise ValueError("one record, one (start, end) and one strand per region")
+
+    def __len__(self) -> int:
+        return self.records.size
+
+    def to_source(self, region_index, position, width) -> Tuple[np.ndarray, np.ndarray]:
+        """A window of ``width`` symbols at ``position`` of derived record ``region_index`` (a hit of a motif of that
+        length) -> ``(source record, source start)``: ``taken_start + position`` on the plus strand,
+        ``taken_end - position - width`` on the minus strand, where the window reads as the reverse complement of the
+        source window that starts there.  Scalars or arrays (broadcast)."""
+        i = np.asarray(region_index, dtype=np.int64)
+        p, w = np.asarray(position, dtype=np.int64), np.asarray(width, dtype=np.int64)
+        plus = self.taken[i, 0] + p
+        minus = self.taken[i, 1] - p - w
+        return self.records[i], np.where(self.strands[i] == 1, minus, plus)
+
+
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data if a.size else np.zeros(2, dtype=np.uint64).ctypes.data
 
@@ -1178,6 +1248,19 @@ class StripedSequenceSet:
             mats.append(CountMatrix(tables[a:a + x * k].reshape(x, k), protein=self.protein))
             a += x * k
         return mats, used.astype(np.int64)
+
+    def regions(self, records, starts, ends, strands=None) -> Tuple["StripedSequenceSet", np.ndarray]:
+        """A set cut out of this one on the device (``lm_hip_seqset_from_regions``): record ``i`` of the result is
+        ``[starts[i], ends[i])`` of record ``records[i]`` (BED: 0-based, half-open), clipped to that record, as it stands or
+        -- where ``strands[i]`` is 1, ``True`` or ``'-'`` (``'+'`` and ``'.'`` count as 0; DNA only) -- as its reverse
+        complement.  Returns the derived set and the ``(n, 2)`` int64 table ``taken`` of what was cut after clipping; a
+        region with an unknown record, or clipped to nothing, gives an empty record and ``(0, 0)``.  ``RegionMap`` maps
+        hits in the derived set back to the source."""
+        reg = _region_args(records, starts, ends, strands)
+        taken = np.zeros((len(reg), 2), dtype=np.uint64)
+        h = C.c_void_p()
+        check(self._pli._L.lm_hip_seqset_from_regions(self._pli._h, self._h, _ptr(reg), len(reg), C.byref(h), _ptr(taken)))
+        return StripedSequenceSet(self._pli, h, self.protein), taken.astype(np.int64)
 
     def records(self) -> List["EncodedSequence"]:
         """Every record read back from the set (``StripedSequence``'s Index, seq.rs:433-442, position by position): one

@@ -62,6 +62,15 @@ then variant in file order, then strand, then motif; ``ref_pos`` / ``alt_pos`` a
 and an allele without a window prints ``.`` for both.  Exit status 2 with a message that names the line: a ``ref`` that is
 not the resident symbol, multi-letter alleles, a non-numeric or zero ``pos`` or one behind the record's end, and, after the
 pass, a ``seq_name`` no record carried.  It excludes ``--best``, ``--counts``, ``--matched`` and ``--site-matrices``.
+``--regions BED`` scans regions of the records instead of the records: the FASTA is ingested as before, and each resident
+set is replaced, before any scan, by the set of the BED rows that name one of its records, cut out on the device
+(``StripedSequenceSet.regions``; ``-`` rows as reverse complements, coordinates clipped to the record).  ``--flank N``
+extends every region by N symbols on both sides, ``--resize W`` centres a window of W symbols on its midpoint.  The output
+is that of a run WITHOUT ``--regions`` on a FASTA file of the extracted regions: a region's record is called by its BED
+name (column 4) or ``chrom:start-end`` -- the coordinates asked for, after ``--flank`` / ``--resize`` -- with ``(-)`` behind a
+minus-strand region; positions are relative to the region as extracted; within a resident set the regions stand in file
+order, and a row whose chromosome no record carries is exit status 2 after the pass.  It excludes ``--variants``
+(variant coordinates would need remapping).
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -357,7 +366,21 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--variants", metavar="PATH",
                     help="score single-symbol variants (TSV: seq_name, 1-based pos, ref, alt) instead of scanning: one line per "
                          "(variant, motif, strand) with a site on at least one allele")
+    ap.add_argument("--regions", metavar="BED",
+                    help="scan regions of the FASTA records instead of the records: a BED file (chrom, 0-based start, end, "
+                         "optional name and strand), cut out of each resident set on the device")
+    resize = ap.add_mutually_exclusive_group()
+    resize.add_argument("--flank", type=int, metavar="N", help="with --regions: extend every region by N symbols on both sides")
+    resize.add_argument("--resize", type=int, metavar="W", help="with --regions: a window of W symbols centred on every region's midpoint")
     return ap
+
+
+def region_names(chroms: Sequence[str], starts: Sequence[int], ends: Sequence[int], strands: Sequence[int],
+                 names: Sequence[Optional[str]]) -> List[str]:
+    """What a region's record is called: its BED name, or ``chrom:start-end`` with the coordinates asked for (after
+    ``--flank`` / ``--resize``, before clipping) and ``(-)`` behind a minus-strand region."""
+    return [name if name is not None else f"{c}:{s}-{e}" + ("(-)" if strand else "")
+            for c, s, e, strand, name in zip(chroms, starts, ends, strands, names)]
 
 
 def log2_mean_odds(total: float, windows: int) -> float:
@@ -395,6 +418,24 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error("--counts excludes --best, --matched and --site-matrices")
     if args.sum_odds and (args.best or args.counts or args.variants or args.matched or args.site_matrices):
         ap.error("--sum-odds excludes --best, --counts, --variants, --matched and --site-matrices")
+    if (args.flank is not None or args.resize is not None) and not args.regions:
+        ap.error("--flank and --resize need --regions")
+    if args.regions and args.variants:
+        ap.error("--regions excludes --variants: variant coordinates would have to be remapped to the regions")
+    if (args.flank is not None and args.flank < 0) or (args.resize is not None and args.resize < 0):
+        ap.error("--flank and --resize take a non-negative number of symbols")
+    bed_by_chrom: dict = {}
+    if args.regions:
+        try:
+            rows = list(lmio.bed_rows(args.regions, args.regions))
+        except (ValueError, OSError) as e:
+            ap.error(str(e))
+        if rows and (args.flank is not None or args.resize is not None):
+            s, e = lmio.resize_regions([r[2] for r in rows], [r[3] for r in rows], flank=args.flank, width=args.resize)
+            rows = [(r[0], r[1], int(a), int(b), r[4], r[5]) for r, a, b in zip(rows, s.tolist(), e.tolist())]
+        for i, row in enumerate(rows):
+            bed_by_chrom.setdefault(row[1], []).append((i,) + row)
+    bed_seen: set = set()
     variants = None
     if args.variants:
         if args.best or args.counts or args.matched or args.site_matrices:
@@ -407,6 +448,30 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pli = Pipeline.hip(args.device)
 
     def sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
+        """One pass over the input: (index of the first record, names, resident set) per chunk -- of the FASTA records, or
+        with --regions of the regions cut out of them."""
+        if not args.regions:
+            yield from record_sets()
+            return
+        first = 0
+        bed_seen.clear()
+        for _, names, seqset in record_sets():
+            picked = []                                  # (row of the file, record of the set, start, end, name, strand)
+            for r, name in enumerate(names):
+                if name in bed_by_chrom and name not in bed_seen:     # (the first record of a name, as read_bed)
+                    bed_seen.add(name)
+                    picked.extend((i, r, s, e, label, strand) for i, _, _, s, e, label, strand in bed_by_chrom[name])
+            if not picked:
+                continue
+            picked.sort()
+            rec, starts, ends = [p[1] for p in picked], [p[2] for p in picked], [p[3] for p in picked]
+            strands = [p[5] for p in picked]
+            derived, _ = seqset.regions(rec, np.array(starts, dtype=np.int64), np.array(ends, dtype=np.int64),
+                                        np.array(strands, dtype=np.uint8))
+            yield first, region_names([names[r] for r in rec], starts, ends, strands, [p[4] for p in picked]), derived
+            first += len(picked)
+
+    def record_sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
         """One pass over the FASTA file: (index of the first record, names, resident set) per chunk."""
         with (_open_bytes if args.ingest == "device" else _open_text)(args.sequences) as fasta:
             if args.ingest == "device":
@@ -557,6 +622,9 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
 
         for first, names, seqset in sets():
             n_hits += (write_counts if args.counts else write_sums if args.sum_odds else write_set)(first, names, seqset)
+        for chrom, rows in bed_by_chrom.items():
+            if chrom not in bed_seen:
+                ap.error(f"{args.regions}:{rows[0][1]}: no record is called `{chrom}`")
         if site_totals is not None:
             if any(int(t.max(initial=0)) > 0xFFFFFFFF for t in site_totals):
                 raise OverflowError("--site-matrices: a site count exceeds the u32 of a count matrix")
