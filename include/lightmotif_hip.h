@@ -772,6 +772,52 @@ typedef struct lm_hip_region_span {
 int lm_hip_seqset_from_regions(lm_hip_ctx *ctx, const lm_hip_seqset *src, const lm_hip_region *regions, size_t n,
                                lm_hip_seqset **out, lm_hip_region_span *taken /* n entries, may be NULL */);
 
+/* A NULL sequence set drawn on the device: EncodedSequence::sample / StripedSequence::sample (seq.rs:131-143,
+ * seq.rs:315-328) for n_records records at once, from a Background (abc.rs:389-402) -- the control every enrichment question
+ * needs, without a host generator and an upload.  Record r has lengths[r] symbols; K = 5 ('D') or 21 ('P').
+ *   uniforms    u(seed, R, j), for position j of record number R = record_base + r (64 bits), is output word j & 3 of the
+ *               Philox4x32-10 block (multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds)
+ *               with key (lo32(seed), hi32(seed)) and counter (lo32(j >> 2), lo32(R), hi32(R), hi32(j >> 2)).  A record's
+ *               text depends on the seed, its number and its own model only -- not on other records, on cols or on how the
+ *               call was launched -- and a longer record extends a shorter one.
+ *   thresholds  of a frequency row f[0 .. K): c_s = the running f64 sum of (double)f[t], t = 0 .. s, in index order;
+ *               T[s] = floor(c_s / c_{K-1} * 2^32) for s < K - 1; draw(T, u) = #{s < K - 1 : u >= T[s]}.  A symbol of
+ *               frequency zero is never drawn.  A row is VALID when every entry is finite and >= 0 and the sum is > 0.
+ *   order 0     transitions == NULL: x_j = draw(T_model(r), u(seed, R, j)); frequencies holds n_models rows of K, one for
+ *               all records (n_models == 1) or one per record (n_models == n_records)
+ *   order 1     transitions != NULL ('D' and n_models == 1 only): frequencies is the `initial` row, transitions K rows of K;
+ *               x_0 = draw(T_initial, u_0), x_j = draw(T_row(x_{j-1}), u_j).  A transition row whose sum is 0 stands for
+ *               `initial` (the N row of a chain fitted on N-free text).
+ *   out         an ordinary lm_hip_seqset on the context's device with `cols` columns and wrap 0: its matrix and offsets
+ *               equal, byte for byte, what lm_hip_seqset_from_encoded builds from the rule's records.  Empty records keep
+ *               their index.
+ * LM_HIP_ERR_BAD_ARGS, before any device work and with a message: a null ctx, out or frequencies; null lengths with
+ * n_records > 0; cols == 0; an alphabet other than 'D' / 'P'; n_models neither 1 nor n_records; transitions with 'P' or with
+ * n_models != 1; a model row that a non-empty record would use and that is not valid (the message names the record or the
+ * row; a transition row is only looked at when a record holds two symbols).  LM_HIP_ERR_CAPACITY when the result would
+ * exceed the 2^40 cells a hit list addresses; LM_HIP_ERR_OOM as lm_hip_seqset_from_encoded.  On any failure *out is NULL.
+ * n_records == 0: a set of zero records; all records empty: n_records empty records; nothing is launched for either.
+ * Enqueues on the context's stream and synchronises it; lm_hip_ctx_last_kernel names the draw kernel afterwards:
+ * "sample_iid" (a lane draws 16 consecutive bytes of the joined text, four per Philox block, and stores them at once) or
+ * "markov_emit" (order 1: the step of a position is a map of the 5 states, 15 bits; three launches in stream order compose
+ * the maps per tile, scan the tiles in one workgroup and replay every lane's run from the symbol that enters it -- no
+ * workgroup waits for another).  lm_hip_sample_tile_bytes: the text bytes one workgroup emits; needs no device.
+ * TEMPORARY DEVICE MEMORY, from the context's scratch: the joined text (its length), 16 bytes per non-empty record, a
+ * threshold row of 32 ('D') or 96 ('P') bytes per non-empty record with per-record models, 5 bytes per tile for order 1. */
+int lm_hip_seqset_sample(lm_hip_ctx *ctx, char alphabet, const uint64_t *lengths, size_t n_records, const float *frequencies,
+                         size_t n_models /* 1, or n_records (order 0 only) */,
+                         const float *transitions /* NULL: order 0; else K*K, 'D' only */, uint64_t seed, uint64_t record_base,
+                         size_t cols, lm_hip_seqset **out);
+size_t lm_hip_sample_tile_bytes(void);
+
+/* Adjacent-pair counts of a set, what a first-order chain is fitted from (the pair statistics behind a Background,
+ * abc.rs:389-402, one order up): counts[a * k + b] = the number of positions p of the concatenation with p and p + 1 in the
+ * same record, symbol a at p and symbol b at p + 1, summed over the set, u64.  Bytes >= k (an adopted matrix) count
+ * nowhere, as in lm_hip_seqset_count_symbols.  Integer arithmetic throughout: a call repeats bit for bit.
+ * LM_HIP_ERR_BAD_ARGS for a null argument or a set on another device; LM_HIP_ERR_CAPACITY when capacity < k * k.
+ * lm_hip_ctx_last_kernel names "pair_blocks" afterwards (nothing is launched for a set of fewer than two symbols). */
+int lm_hip_seqset_count_pairs(lm_hip_ctx *ctx, const lm_hip_seqset *set, uint64_t *counts, size_t capacity);
+
 /* ScoreDistribution of n matrices at once (pwm/dist.rs:51-226, `ScoringMatrix::to_score_distribution`
  * pwm/mod.rs:698-705): what turns the CLI's `--pvalue` into thresholds (main.rs:479-489) and a hit's score into the
  * `pvalue` column (main.rs:335), built and queried on the device (csrc/dist.hip) instead of motif by motif, hit by hit on

@@ -155,6 +155,9 @@ SIGNATURES = {
     "lm_hip_seqset_variant_effects": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, _vp, _sz, _vp, _vp]),
     "lm_hip_seqset_variant_hits": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, _vp, _sz, _vp, C.POINTER(_vp), _vp]),
     "lm_hip_seqset_from_regions": (C.c_int, [_vp, _vp, _vp, _sz, C.POINTER(_vp), _vp]),
+    "lm_hip_seqset_sample": (C.c_int, [_vp, C.c_char, _vp, _sz, _vp, _sz, _vp, C.c_uint64, C.c_uint64, _sz, C.POINTER(_vp)]),
+    "lm_hip_sample_tile_bytes": (_sz, []),
+    "lm_hip_seqset_count_pairs": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_dists_create": (C.c_int, [_vp, C.POINTER(_vp), _sz, C.POINTER(_vp), C.POINTER(_vp)]),
     "lm_hip_dists_len": (_sz, [_vp]),
     "lm_hip_dists_info": (C.c_int, [_vp, _sz, _szp, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _szp]),

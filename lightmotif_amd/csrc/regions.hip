@@ -26,6 +26,7 @@
 #include <string>
 #include <vector>
 
+#include "live_search.hpp"
 #include "lm_internal.hpp"
 #include "regions_plan.hpp"
 
@@ -36,20 +37,6 @@ namespace regions {
 __device__ __forceinline__ unsigned long long div_u64(unsigned long long a, unsigned long long b)
 {
     return ((a | b) >> 32) ? a / b : (unsigned long long)((unsigned)a / (unsigned)b);
-}
-
-// largest s in [lo, hi) with dst[s] <= x (dst[lo] <= x)
-template <class Off>
-__device__ __forceinline__ unsigned long long find_live(const Off &dst, unsigned long long lo, unsigned long long hi, unsigned long long x)
-{
-    while (hi - lo > 1) {
-        const unsigned long long mid = lo + (hi - lo) / 2;
-        if (dst(mid) <= x)
-            lo = mid;
-        else
-            hi = mid;
-    }
-    return lo;
 }
 
 // Where a lane stands in the source matrix, and how it moves on to the next symbol of its region.

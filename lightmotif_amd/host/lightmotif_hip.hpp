@@ -219,6 +219,13 @@ public:
     // stated; main.rs:532-546): the host uploads `size` bytes and never looks at a sequence line.  Strict mode throws
     // InvalidSymbol(record, index) for the first residue outside the alphabet.
     static SequenceSet from_fasta(const Pipeline<A> &pipeline, const void *data, size_t size, bool lossy = false, size_t columns = 32);
+    // A null set drawn on the device (lm_hip_seqset_sample, where the rule is stated; seq.rs:131-143, seq.rs:315-328): record r
+    // holds lengths[r] symbols drawn from `frequencies` -- A::K values for all records or lengths.size() * A::K, one row per
+    // record -- or, with `transitions` (A::K * A::K, DNA only, one model per call), from the first-order chain that starts in
+    // `frequencies`.  A record's text depends on seed, record_base + r and its model alone.
+    static SequenceSet sample(const Pipeline<A> &pipeline, const std::vector<uint64_t> &lengths, const std::vector<float> &frequencies,
+                              const std::vector<float> *transitions = nullptr, uint64_t seed = 0, uint64_t record_base = 0,
+                              size_t columns = 32);
     // ... per record the bytes [begin, end) of the input that hold its header line, without the '>' and the '\n' (empty for
     // sets made otherwise)
     const std::vector<lm_hip_fasta_span> &header_spans() const { return spans_; }
@@ -249,6 +256,14 @@ public:
         std::vector<uint64_t> out(records() * A::K);
         uint64_t none = 0;
         check(lm_hip_seqset_count_symbols(ctx_->ctx, h_, out.empty() ? &none : out.data(), out.size()));
+        return out;
+    }
+    // Adjacent-pair counts (lm_hip_seqset_count_pairs): A::K x A::K, row-major; [a][b] counts the positions with symbol a whose
+    // successor in the same record is b
+    std::vector<uint64_t> count_pairs() const
+    {
+        std::vector<uint64_t> out(A::K * A::K);
+        check(lm_hip_seqset_count_pairs(ctx_->ctx, h_, out.data(), out.size()));
         return out;
     }
     // Symbols read back out of the set (csrc/sites.hip).  A site names the window [position + shift, position + shift + width)
@@ -1655,6 +1670,22 @@ public:
         lm_hip_free(raw);
         return SequenceSet<A>(ctx_, h, std::move(spans));
     }
+    // ... drawn on the device (lm_hip_seqset_sample): SequenceSet::sample
+    SequenceSet<A> sample_set(const std::vector<uint64_t> &lengths, const std::vector<float> &frequencies,
+                              const std::vector<float> *transitions = nullptr, uint64_t seed = 0, uint64_t record_base = 0,
+                              size_t columns = 32) const
+    {
+        if (frequencies.size() != A::K && frequencies.size() != lengths.size() * A::K)
+            throw std::invalid_argument("sample_set: A::K frequencies, or A::K per record");
+        if (transitions && transitions->size() != A::K * A::K)
+            throw std::invalid_argument("sample_set: transitions are A::K x A::K");
+        const size_t n_models = frequencies.size() == A::K && lengths.size() != 1 ? 1 : lengths.size();
+        const uint64_t none = 0;
+        lm_hip_seqset *h = nullptr;
+        check(lm_hip_seqset_sample(ctx_->ctx, A::code, lengths.empty() ? &none : lengths.data(), lengths.size(), frequencies.data(),
+                                   n_models, transitions ? transitions->data() : nullptr, seed, record_base, columns, &h));
+        return SequenceSet<A>(ctx_, h);
+    }
     // ... from encoded records (lm_hip_seqset_from_encoded)
     SequenceSet<A> stripe_set(const std::vector<EncodedSequence<A>> &records, size_t columns = 32) const
     {
@@ -1806,6 +1837,13 @@ template <class A>
 SequenceSet<A> SequenceSet<A>::from_fasta(const Pipeline<A> &pipeline, const void *data, size_t size, bool lossy, size_t columns)
 {
     return pipeline.stripe_fasta_set(data, size, lossy, columns);
+}
+
+template <class A>
+SequenceSet<A> SequenceSet<A>::sample(const Pipeline<A> &pipeline, const std::vector<uint64_t> &lengths, const std::vector<float> &frequencies,
+                                      const std::vector<float> *transitions, uint64_t seed, uint64_t record_base, size_t columns)
+{
+    return pipeline.sample_set(lengths, frequencies, transitions, seed, record_base, columns);
 }
 
 // The merge rule on host arrays (any transport): per-shard results in ascending row order, rows

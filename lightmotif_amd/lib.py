@@ -17,6 +17,7 @@ in the hand-written gfx950 kernels.  Nothing here falls back to the CPU.
 from __future__ import annotations
 
 import ctypes as C
+import math
 from typing import Dict, Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
@@ -27,7 +28,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 __all__ = [
     "pack_2bit", "fasta_names",
     "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "RegionMap", "SetHits", "SetBest", "SetCounts", "SetSums", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
-    "background_from_counts", "decode",
+    "background_from_counts", "markov_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
 ]
@@ -355,6 +356,32 @@ class Pipeline:
         h = C.c_void_p()
         check(self._L.lm_hip_seqset_from_encoded(self._h, buf.ctypes.data if buf.size else None, buf.size, offs.ctypes.data,
                                                  offs.size - 1, columns, _k(protein), C.byref(h)))
+        return StripedSequenceSet(self, h, protein)
+
+    def sample_set(self, lengths, background, transitions=None, *, seed: int = 0, record_base: int = 0, protein: bool = False,
+                   columns: int = DEFAULT_COLUMNS) -> "StripedSequenceSet":
+        """A null set drawn on the device (``lm_hip_seqset_sample``; seq.rs:131-143, seq.rs:315-328 for every record at once):
+        record ``r`` holds ``lengths[r]`` symbols drawn from ``background`` -- ``k`` f32 frequencies for all records, or a
+        ``(records, k)`` table with one row per record -- or, with ``transitions`` (``(k, k)``, DNA only, one model per call),
+        from the first-order chain that starts in ``background``.  A record's text depends on ``seed``, on its number
+        ``record_base + r`` and on its model alone; the header spells out the rule, which a numpy restatement reproduces bit
+        for bit."""
+        k = _k(protein)
+        n = _u64_array(lengths)
+        f = np.ascontiguousarray(background, dtype=np.float32)
+        if f.ndim not in (1, 2) or f.shape[-1] != k:
+            raise ValueError(f"background: {k} frequencies, or a (records, {k}) table")
+        if f.ndim == 2 and f.shape[0] != n.size:
+            raise ValueError(f"{f.shape[0]} models for {n.size} records")
+        t = None
+        if transitions is not None:
+            t = np.ascontiguousarray(transitions, dtype=np.float32)
+            if t.shape != (k, k):
+                raise ValueError(f"transitions: a ({k}, {k}) table")
+        h = C.c_void_p()
+        check(self._L.lm_hip_seqset_sample(self._h, b"P" if protein else b"D", _ptr(n), n.size, _ptr(f), 1 if f.ndim == 1 else n.size,
+                                           t.ctypes.data if t is not None else None, int(seed) % (1 << 64),
+                                           int(record_base) % (1 << 64), columns, C.byref(h)))
         return StripedSequenceSet(self, h, protein)
 
     def scan_threshold_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], thresholds: Optional[Sequence[float]],
@@ -831,6 +858,35 @@ def background_from_counts(counts, unknown: bool = False) -> np.ndarray:
     return table.astype(np.float32) / total.astype(np.float32)
 
 
+def markov_from_counts(symbol_counts, pair_counts, pseudocount: float = 0.0, unknown: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """A first-order chain ``(initial, transitions)`` from the symbol counts (``count_symbols``) and adjacent-pair counts
+    (``count_pairs``) of a set, for ``Pipeline.sample_set``.  ``initial`` is ``background_from_counts`` of the summed symbol
+    counts.  ``transitions[a][b]`` is ``pair[a][b] + pseudocount`` over the total of row ``a``: entry and total are formed in
+    f64 (exact for counts), converted to f32 once each and divided in f32, as ``background_from_counts`` does.  A row without
+    counts is zeros, which the sampler reads as ``initial``.  Without ``unknown`` the default symbol's row and column are
+    zero."""
+    initial = background_from_counts(symbol_counts, unknown)
+    k = initial.size
+    pairs = np.asarray(pair_counts)
+    if pairs.dtype.kind not in "iu":
+        raise TypeError("pair counts are integers")
+    if pairs.size != k * k:
+        raise ValueError(f"pair counts: a ({k}, {k}) table")
+    if (pairs < 0).any():
+        raise ValueError("pair counts cannot be negative")
+    if not pseudocount >= 0:
+        raise ValueError("a pseudocount is not negative")
+    table = pairs.reshape(k, k).astype(np.float64) + float(pseudocount)
+    if not unknown:
+        table[-1, :] = 0
+        table[:, -1] = 0
+    totals = np.array([math.fsum(row) for row in table.tolist()], dtype=np.float64).astype(np.float32)
+    transitions = np.zeros((k, k), dtype=np.float32)
+    live = totals > 0
+    transitions[live] = table[live].astype(np.float32) / totals[live, None]
+    return initial, transitions
+
+
 def _count_symbols(call, ctx, handle, records: int, k: int) -> np.ndarray:
     out = np.zeros(records * k, dtype=np.int64)     # (the library writes u64: a count never reaches 2^63)
     # (an empty table still needs a pointer: NULL is a misuse of the entry point, zero records are not)
@@ -1198,6 +1254,35 @@ class StripedSequenceSet:
     def background(self, unknown: bool = False) -> np.ndarray:
         """``Background::from_sequences`` (abc.rs:441-456) of the set's records: ``k`` f32 frequencies."""
         return background_from_counts(self.count_symbols(), unknown)
+
+    def count_pairs(self) -> np.ndarray:
+        """Adjacent-pair counts of the set (``lm_hip_seqset_count_pairs``): a ``(k, k)`` int64 table, ``[a, b]`` the number of
+        positions whose symbol is ``a`` and whose successor IN THE SAME RECORD is ``b``."""
+        k = _k(self.protein)
+        out = np.zeros(k * k, dtype=np.int64)
+        check(self._pli._L.lm_hip_seqset_count_pairs(self._pli._h, self._h, out.ctypes.data, out.size))
+        return out.reshape(k, k)
+
+    def null(self, order: int = 0, *, seed: int = 0, record_base: int = 0) -> "StripedSequenceSet":
+        """A control for this set, drawn on the device (``Pipeline.sample_set``): the same record lengths and columns, and
+        order 0 -- every record from its OWN composition (``count_symbols``, the default symbol included, so that N-rich
+        records stay N-rich; an empty record uses no model); order 1 (DNA) -- every record from the one chain fitted on the
+        whole set (``markov_from_counts`` of ``count_symbols`` and ``count_pairs``)."""
+        lengths = self.lengths
+        if order == 0:
+            counts = self.count_symbols()
+            model = counts.astype(np.float32) / np.maximum(counts.sum(axis=1), 1).astype(np.float32)[:, None]
+            return self._pli.sample_set(lengths, model, seed=seed, record_base=record_base, protein=self.protein, columns=self.columns)
+        if order != 1:
+            raise ValueError("order 0 (i.i.d.) or 1 (first-order Markov)")
+        if not lengths.any():
+            initial, transitions = uniform_background(_k(self.protein)), np.zeros((_k(self.protein),) * 2, dtype=np.float32)
+        else:
+            counts = self.count_symbols()
+            unknown = not counts[:, :-1].any()      # nothing but the default symbol: it is the model
+            initial, transitions = markov_from_counts(counts, self.count_pairs(), unknown=unknown)
+        return self._pli.sample_set(lengths, initial, transitions, seed=seed, record_base=record_base, protein=self.protein,
+                                    columns=self.columns)
 
     def windows(self, sites, widths, shifts=0) -> List[Tuple[np.ndarray, np.ndarray]]:
         """The symbols of the windows ``[position + shift, position + shift + width)`` of the given sites, read out of the

@@ -71,6 +71,12 @@ name (column 4) or ``chrom:start-end`` -- the coordinates asked for, after ``--f
 minus-strand region; positions are relative to the region as extracted; within a resident set the regions stand in file
 order, and a row whose chromosome no record carries is exit status 2 after the pass.  It excludes ``--variants``
 (variant coordinates would need remapping).
+``--null order0|order1`` scans a CONTROL instead of the input: each resident set (after ``--regions``, if given) is replaced,
+before any scan, by ``StripedSequenceSet.null`` of itself -- records of the same names and lengths drawn on the device.
+``order0`` draws every record i.i.d. from its own composition (``N`` included); the generator numbers a record by its index
+in the whole input, so the output does not depend on ``--batch-bases``.  ``order1`` fits ONE first-order Markov chain per
+resident set, i.e. per ``--batch-bases`` chunk.  ``--null-seed N`` (default 0) seeds the generator.  It excludes
+``--variants``, ``--matched`` and ``--site-matrices``, which ask about the real text.
 ``--reverse`` also scans the reverse-complement matrix and reports strand ``-``
 (main.rs:343-362).  There is no CPU path: without a gfx950 device the scan fails.
 """
@@ -327,6 +333,9 @@ def variant_lines(pli: Pipeline, seqset: StripedSequenceSet, names: Sequence[str
     return [row[3] for row in rows]
 
 
+NULL_ORDERS = {"order0": 0, "order1": 1}
+
+
 def build_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="lightmotif_amd.scan_cli", description=__doc__.split("\n\n")[0])
     ap.add_argument("-m", "--matrices", required=True, help="JASPAR-2016 count matrices (optionally gzipped)")
@@ -366,6 +375,12 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--variants", metavar="PATH",
                     help="score single-symbol variants (TSV: seq_name, 1-based pos, ref, alt) instead of scanning: one line per "
                          "(variant, motif, strand) with a site on at least one allele")
+    ap.add_argument("--null", choices=sorted(NULL_ORDERS),
+                    help="scan a control instead of the input: every resident set is replaced by a set of the same names and lengths "
+                         "drawn on the device -- order0: every record i.i.d. from its own composition (N included), so the output "
+                         "does not depend on --batch-bases; order1: a first-order Markov chain, ONE chain fitted per resident set "
+                         "(per --batch-bases chunk).  Excludes --variants, --matched and --site-matrices, which ask about the real text")
+    ap.add_argument("--null-seed", type=int, default=0, metavar="N", help="with --null: the seed of the generator (default 0)")
     ap.add_argument("--regions", metavar="BED",
                     help="scan regions of the FASTA records instead of the records: a BED file (chrom, 0-based start, end, "
                          "optional name and strand), cut out of each resident set on the device")
@@ -418,6 +433,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
             ap.error("--counts excludes --best, --matched and --site-matrices")
     if args.sum_odds and (args.best or args.counts or args.variants or args.matched or args.site_matrices):
         ap.error("--sum-odds excludes --best, --counts, --variants, --matched and --site-matrices")
+    if args.null is not None and (args.variants or args.matched or args.site_matrices):
+        ap.error("--null excludes --variants, --matched and --site-matrices: those ask about the real text")
+    if args.null_seed < 0:
+        ap.error("--null-seed is not negative")
     if (args.flank is not None or args.resize is not None) and not args.regions:
         ap.error("--flank and --resize need --regions")
     if args.regions and args.variants:
@@ -448,6 +467,15 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     pli = Pipeline.hip(args.device)
 
     def sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
+        """One pass over the input, as it stands or -- with --null -- every set replaced by its control: same names, same
+        lengths; the record number of the generator is the record's index in the whole input."""
+        if args.null is None:
+            yield from input_sets()
+            return
+        for first, names, seqset in input_sets():
+            yield first, names, seqset.null(NULL_ORDERS[args.null], seed=args.null_seed, record_base=first)
+
+    def input_sets() -> Iterator[Tuple[int, List[str], StripedSequenceSet]]:
         """One pass over the input: (index of the first record, names, resident set) per chunk -- of the FASTA records, or
         with --regions of the regions cut out of them."""
         if not args.regions:
