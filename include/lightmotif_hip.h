@@ -601,6 +601,40 @@ int lm_hip_scan_count_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, c
 int lm_hip_scan_sum_seqset(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *scales, size_t n,
                            const lm_hip_seqset *set, double *sums);
 
+/* The expected site counts of every motif over the set, in ONE call: the E-step of motif EM (MEME's OOPS / ZOOPS), the
+ * deterministic form of the sampler's step "score the record, weigh every window by 2^(score / temperature), rebuild the
+ * count matrix" (sampler.rs:528-538 with CountMatrix::from_sequences, pwm/mod.rs:209-237; the windows of a RECORD as
+ * scan.rs:185-190).  For motif i (M rows, scale s_i) a table of M x K doubles
+ *       E[j][s] = sum over records r and windows p of z(r, p) * [symbol(r, p + j) == s]
+ *   windows   of record r: the positions p with p + M <= len(r)
+ *   v         the window score exactly as score_into gives it: M sequential f32 adds from +0.0 in row order, bit for bit
+ *             the score lm_hip_scan_best_seqset, lm_hip_scan_count_seqset and lm_hip_scan_sum_seqset see
+ *   e         exp2_wide(fl32(s_i * v)), the term of lm_hip_scan_sum_seqset (csrc/seqset_sum_plan.hpp)
+ *   z         min(e * gains[i * records + r], 1.0) in f64: the posterior of the window.  A window whose score is NaN, or
+ *             whose product e * gain is NaN (+inf * 0), contributes nothing; -inf scores give 0, +inf scores 1
+ *   q         (u64) rint(z * 2^F), round to nearest even, F = min(40, 62 - bit_length(N)), N the positions of the set: F
+ *             is a function of the set alone and no cell can overflow 64 bits (z <= 1, a cell sums at most N windows)
+ *   Q[j][s]   the sum of q over the windows whose symbol at offset j is s: an exact integer;  E = (double) Q * 2^-F
+ *   scales    n of them, or NULL: all 1 (1 / temperature), finite and > 0 as for lm_hip_scan_sum_seqset
+ *   gains     n * records doubles, row-major, each finite and >= 0; gain 0 switches a record off.  1 / Z_r with Z the
+ *             cell of lm_hip_scan_sum_seqset is the OOPS posterior
+ *   counts    the caller's memory: the n tables of M_i x K doubles, row-major, one behind the other; K is the alphabet's
+ *             size with its default symbol (5 / 21), as in a CountMatrix.  Every cell is written
+ *   frac_bits NULL, or where F goes
+ * Integer additions have no order, so the tables are a pure function of (set, matrix, scale, gains): the same bits from
+ * run to run, at any rows_per_stream and with any number of motifs in the call; no floating-point atomic is used.  A
+ * window with q == 0 is skipped, exactly.  Every row j of a motif's Q has the same total, the sum of q over its windows.
+ * One kernel for every motif length (csrc/seqset_expect.hip on the record walk of csrc/seqset_walk.hpp;
+ * lm_hip_ctx_last_kernel names `seqset_expect_generic`): a workgroup gathers its windows into a table of u64 counters in
+ * LDS and adds the non-zero ones to Q with 64-bit integer atomics.  A motif with no window anywhere returns zeros.
+ * LM_HIP_ERR_WRAP when the set's wrap < max(M) - 1; LM_HIP_ERR_BAD_ARGS, before any launch, on null arguments (null
+ * `gains` or `counts` when n > 0 and the set has records), a matrix whose alphabet size differs from the set's, a scale
+ * that is not finite or not > 0, or a gain that is NaN, infinite or negative; LM_HIP_OK with no table written when n == 0
+ * or the set has no records. */
+int lm_hip_seqset_expected_counts(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const float *scales,
+                                  const double *gains, size_t n, const lm_hip_seqset *set, double *counts,
+                                  int *frac_bits);
+
 /* SymbolCount::count_symbols of a StripedSequence (seq.rs:444-483, the loop of seq.rs:466-482), and the same for every
  * record of a set in ONE call: what Background::from_sequence / from_sequences (abc.rs:404-456) count before
  * Background::from_counts (abc.rs:389-402) turns the table into frequencies, on the resident bytes (csrc/composition.hip).

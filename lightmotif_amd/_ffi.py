@@ -148,6 +148,8 @@ SIGNATURES = {
     "lm_hip_scan_best_seqset": (C.c_int, [_vp, C.POINTER(_vp), _sz, _vp, C.POINTER(SetBest)]),
     "lm_hip_scan_count_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _sz, _vp, C.POINTER(C.c_uint32)]),
     "lm_hip_scan_sum_seqset": (C.c_int, [_vp, C.POINTER(_vp), _fp, _sz, _vp, C.POINTER(C.c_double)]),
+    "lm_hip_seqset_expected_counts": (C.c_int, [_vp, C.POINTER(_vp), _fp, C.POINTER(C.c_double), _sz, _vp, C.POINTER(C.c_double),
+                                                C.POINTER(C.c_int)]),
     "lm_hip_seq_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_count_symbols": (C.c_int, [_vp, _vp, _vp, _sz]),
     "lm_hip_seqset_windows": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _sz, _vp, _sz, _vp, _sz, _vp]),

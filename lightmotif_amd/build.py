@@ -36,7 +36,7 @@ LONG_FLAGS = ["-mllvm", "-pragma-unroll-threshold=10000000"]
 XLONG = list(range(72, 89, 8))
 # score_pair_inst.hip: the pair-symbol prefilter scan alone for the lengths beyond the exact kernels (65 ... 128)
 PAIR = [(65, 80), (81, 96), (97, 112), (113, 128)]
-UNITS = ["score_plan.hip", "score_store.hip", "score_argmax.hip", "score_argmax_exact.hip", "score_argmax_cand.hip", "score_threshold.hip", "reduce.hip", "hits.hip", "seqset.hip", "seqset_best.hip", "seqset_count.hip", "seqset_sum.hip", "fasta.hip", "dist.hip", "composition.hip", "sites.hip", "variants.hip", "regions.hip", "sample.hip", "pairs.hip", "discrete.hip", "layout.hip", "scanmax.hip", "context.hip", "pssm.hip", "score_api.hip", "handles.hip",
+UNITS = ["score_plan.hip", "score_store.hip", "score_argmax.hip", "score_argmax_exact.hip", "score_argmax_cand.hip", "score_threshold.hip", "reduce.hip", "hits.hip", "seqset.hip", "seqset_best.hip", "seqset_count.hip", "seqset_sum.hip", "seqset_expect.hip", "fasta.hip", "dist.hip", "composition.hip", "sites.hip", "variants.hip", "regions.hip", "sample.hip", "pairs.hip", "discrete.hip", "layout.hip", "scanmax.hip", "context.hip", "pssm.hip", "score_api.hip", "handles.hip",
          "hostptr.hip", "host_lane.hip", "host_pipe.hip", "host_cost.hip", "comm.hip"]
 # seqset_best.hip, seqset_count.hip and seqset_sum.hip unroll M steps of M adds for every M up to 36: the same raised
 # unroll budget

@@ -1,20 +1,34 @@
 // seqset_walk_launch.hpp -- the host half of the record walk (seqset_walk.hpp): the table of a route's fused kernels, the
 // rows a lane walks, the launcher and the checks of an entry point, once for seqset_best.hip, seqset_count.hip and
-// seqset_sum.hip.
+// seqset_sum.hip, and for seqset_expect.hip.
 //
 // A route describes itself with a struct W: Job (an entry of the job table, { dense, slot_base, ... }), Slot (what the
 // kernels merge into), kName ("seqset_best": the kernels are <kName>_fused<M> and <kName>_generic), kTally (registry family
-// tallied per fused launch, -1: none), fused<M>() and generic() (the __global__ functions).
+// tallied per fused launch, -1: none), fused<M>() and generic() (the __global__ functions).  A route that keeps a table
+// of its own in LDS behind the weights and the offsets declares table_lds(staged bytes, m, k), the bytes of it (0: it
+// does not fit); such a route has one body, the generic one, for every motif length (seqset_expect.hip).
 #pragma once
 
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <type_traits>
 
 #include "score_launch.hpp"
 #include "seqset_walk.hpp"
 
 namespace lm {
+
+template <typename W, typename = void>
+struct WalkTable {
+    static constexpr bool kOwn = false;
+    static size_t lds(size_t, size_t, size_t) { return 0; }
+};
+template <typename W>
+struct WalkTable<W, std::void_t<decltype(&W::table_lds)>> {
+    static constexpr bool kOwn = true;
+    static size_t lds(size_t staged, size_t m, size_t k) { return W::table_lds(staged, m, k); }
+};
 
 template <typename W>
 struct WalkKernels {
@@ -129,7 +143,7 @@ int launch_walk(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const char *de
                 caller.push_back(i - c0);
             }
         const std::vector<JobGroup> groups = group_jobs(ctx, args.data(), args.size(), [&](size_t i) {
-            return args[i].pssm->m <= (size_t)kMaxFastM ? KIND_EXACT : KIND_GENERIC;
+            return !WalkTable<W>::kOwn && args[i].pssm->m <= (size_t)kMaxFastM ? KIND_EXACT : KIND_GENERIC;
         });
         table.clear();
         std::vector<size_t> first(groups.size());
@@ -169,7 +183,8 @@ int launch_walk(lm_hip_ctx *ctx, const lm_hip_pssm *const *pssms, const char *de
             } else {
                 const size_t wbytes = p->m * p->k * sizeof(float);
                 const int w_lds = wbytes + off_bytes <= 60 * 1024;
-                const size_t lds = std::max<size_t>((w_lds ? (wbytes + 15) & ~(size_t)15 : 0) + off_bytes, 16);
+                const size_t staged = (w_lds ? (wbytes + 15) & ~(size_t)15 : 0) + off_bytes;
+                const size_t lds = std::max<size_t>(staged + WalkTable<W>::lds(staged, p->m, p->k), 16);
                 hipLaunchKernelGGL(W::generic(), grid, dim3(kBlock), lds, st, seq->d_data, (unsigned long long)seq->stride,
                                    (unsigned)seq->cols, (unsigned long long)seq->rows, (unsigned)p->m, (unsigned)p->k, w_lds,
                                    d_jobs + first[gi], set->d_offsets, (unsigned long long)records, (int)off_lds, T, d_slots);

@@ -1801,6 +1801,42 @@ public:
             out[i].assign(flat.begin() + i * records, flat.begin() + (i + 1) * records);
         return out;
     }
+    // The expected site counts of every motif over a set in one call (lm_hip_seqset_expected_counts), the E-step of
+    // motif EM: tables[i] is the M_i x K table, row-major, of the sums of z = min(2^(scale_i * score) * gains[i][r], 1)
+    // over the windows of every record r whose symbol at offset j is s, quantised to 2^-frac_bits and summed as integers
+    // on the device (bit-identical from call to call).  `gains` holds one row of `records` finite gains >= 0 per motif
+    // (1 / scan_sum for one site per record); `scales` as for scan_sum.
+    struct ExpectedCounts {
+        std::vector<std::vector<double>> tables;
+        int frac_bits = 0;
+    };
+    ExpectedCounts expected_counts(const std::vector<const ScoringMatrix<A> *> &pssms, const SequenceSet<A> &set,
+                                   const std::vector<std::vector<double>> &gains, const std::vector<float> &scales = {}) const
+    {
+        const size_t n = pssms.size(), records = set.records();
+        if (!scales.empty() && scales.size() != n)
+            throw std::invalid_argument("no scales, or one per motif");
+        if (gains.size() != n)
+            throw std::invalid_argument("one row of gains per motif");
+        std::vector<const lm_hip_pssm *> handles(n);
+        std::vector<double> flat_gains(n * records);
+        size_t cells = 0;
+        for (size_t i = 0; i < n; ++i) {
+            if (gains[i].size() != records)
+                throw std::invalid_argument("one gain per record");
+            std::copy(gains[i].begin(), gains[i].end(), flat_gains.begin() + i * records);
+            handles[i] = pssms[i]->device(ctx_->ctx);
+            cells += pssms[i]->len() * A::K;
+        }
+        std::vector<double> flat(cells);
+        ExpectedCounts out;
+        check(lm_hip_seqset_expected_counts(ctx_->ctx, handles.data(), scales.empty() ? nullptr : scales.data(), flat_gains.data(), n,
+                                            set.handle(), flat.data(), &out.frac_bits));
+        out.tables.resize(n);
+        for (size_t i = 0, at = 0; i < n; at += pssms[i]->len() * A::K, ++i)
+            out.tables[i].assign(flat.begin() + at, flat.begin() + at + pssms[i]->len() * A::K);
+        return out;
+    }
 
     // ---- row-sharded jobs across the GPUs of a node -----------------------------------
     // Score::score_rows_into takes a row range so that a sequence can be cut (pli/mod.rs:72-78):

@@ -27,7 +27,7 @@ from ._ffi import Coords, InvalidSymbol, LightmotifHipError, SetHit, Unsupported
 
 __all__ = [
     "pack_2bit", "fasta_names",
-    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "RegionMap", "SetHits", "SetBest", "SetCounts", "SetSums", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
+    "Pipeline", "EncodedSequence", "StripedSequence", "StripedSequenceSet", "RegionMap", "SetHits", "SetBest", "SetCounts", "SetSums", "SetExpectedCounts", "posterior_gains", "expected_to_scoring", "SetVariantEffects", "SetVariantHits", "ScoreDistributions", "CountMatrix", "WeightMatrix",
     "background_from_counts", "markov_from_counts", "decode",
     "ScoringMatrix", "DiscreteMatrix", "StripedScores", "Scanner", "Hit", "Motif", "create", "stripe", "scan",
     "UnsupportedBackend", "InvalidSymbol", "LightmotifHipError", "DEFAULT_COLUMNS",
@@ -462,6 +462,76 @@ class Pipeline:
         lengths = seqset.lengths.reshape(1, -1)
         rows = np.asarray([len(p) for p in batch.pssms], dtype=np.int64).reshape(-1, 1)
         return SetSums(sums, np.maximum(0, lengths - rows + 1), self.last_kernel if sums.size else "")
+
+    def expected_counts_set(self, pssms: Union[Sequence["ScoringMatrix"], "MotifBatch"], seqset: "StripedSequenceSet", gains,
+                            scale=None) -> "SetExpectedCounts":
+        """The expected site counts of every motif over the set in one call (``lm_hip_seqset_expected_counts``), the E-step
+        of motif EM: per motif the ``(M, K)`` table ``E[j][s] = sum of z over the windows whose symbol at offset j is s``,
+        ``z = min(2 ** (scale * score) * gains[motif, record], 1)`` quantised to ``2 ** -frac_bits``.  ``gains`` is
+        ``(motifs, records)`` float64, finite and >= 0 (``posterior_gains`` of ``scan_sum_set``); ``scale`` as for
+        ``scan_sum_set``.  The tables are a pure function of the inputs: integer sums on the device, no order."""
+        batch = pssms if isinstance(pssms, MotifBatch) else MotifBatch(self, pssms)
+        if batch.protein - {seqset.protein}:
+            _same_alphabet(next(p for p in batch.pssms if p.protein != seqset.protein), seqset)
+        n, records, k = len(batch), len(seqset), _k(seqset.protein)
+        scales = None
+        if scale is not None:
+            scales = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32), (n,)) if np.ndim(scale) == 0 else scale,
+                                          dtype=np.float32)
+            if scales.shape != (n,):
+                raise ValueError("scale: one number, or one per motif")
+        g = np.ascontiguousarray(gains, dtype=np.float64)
+        if g.shape != (n, records):
+            raise ValueError(f"gains: a ({n}, {records}) table, one gain per motif and record")
+        rows = [len(p) for p in batch.pssms]
+        flat = np.zeros(sum(rows) * k, dtype=np.float64)
+        frac = C.c_int(0)
+        check(self._L.lm_hip_seqset_expected_counts(self._h, batch.handles, scales.ctypes.data_as(C.POINTER(C.c_float)) if scales is not None else None,
+                                                    g.ctypes.data_as(C.POINTER(C.c_double)) if g.size else None, n, seqset._h,
+                                                    flat.ctypes.data_as(C.POINTER(C.c_double)) if flat.size else None, C.byref(frac)))
+        cuts = np.cumsum([0] + [m * k for m in rows])
+        tables = [flat[cuts[i]:cuts[i + 1]].reshape(rows[i], k) for i in range(n)]
+        return SetExpectedCounts(tables, int(frac.value), self.last_kernel if n and records else "")
+
+    def em_step(self, pssms: Sequence["ScoringMatrix"], seqset: "StripedSequenceSet", model: str = "oops", gamma=None, scale=None,
+                pseudocount: Union[None, float, Dict[str, float]] = 0.1, background=None):
+        """One iteration of motif EM on the resident set: ``scan_sum_set`` (Z per record), ``posterior_gains``,
+        ``expected_counts_set`` (the E-step) and ``expected_to_scoring`` (the M-step, the f32 arithmetic of
+        ``CountMatrix.to_scoring``).  Returns ``(matrices, expected, gamma, log2_likelihood)``: the new ``ScoringMatrix``
+        objects, the ``SetExpectedCounts``, for ZOOPS the new ``gamma`` per motif (the mean posterior mass per record
+        with a window; None for OOPS) and the log2-likelihood ratio of the matrices that came IN, per motif: the sum over
+        the records with a window of ``log2 Z_r`` (OOPS) or ``log2((1 - gamma) + lambda_r Z_r)`` (ZOOPS).  ``background``
+        defaults to the set's own (``seqset.background()``)."""
+        pssms = list(pssms)
+        sums = self.scan_sum_set(pssms, seqset, scale)
+        gains = posterior_gains(sums, model, gamma)
+        expected = self.expected_counts_set(pssms, seqset, gains, scale)
+        bg = seqset.background() if background is None else background
+        new = [expected_to_scoring(c, pseudocount, bg, protein=seqset.protein) for c in expected.counts]
+        ll, new_gamma = _em_likelihood(sums, gains, model, gamma)
+        return new, expected, new_gamma, ll
+
+    def refine(self, pssms: Sequence["ScoringMatrix"], seqset: "StripedSequenceSet", iterations: int, model: str = "oops", gamma=None,
+               scale=None, pseudocount: Union[None, float, Dict[str, float]] = 0.1, background=None, return_counts: bool = False):
+        """``iterations`` calls of ``em_step``, each on the matrices of the one before.  Returns ``(matrices,
+        log2_likelihood)``: the refined matrices and an ``(iterations + 1, motifs)`` float64 table, row ``t`` the
+        log2-likelihood of the matrices after ``t`` iterations (row 0: as given), which EM does not let decrease beyond the
+        fixed point's quantisation.  For ZOOPS ``gamma`` (default 0.5) is re-estimated at every iteration.  With
+        ``return_counts`` a third value follows: the ``SetExpectedCounts`` of the last iteration (None without one)."""
+        mats = list(pssms)
+        if model == "zoops" and gamma is None:
+            gamma = 0.5
+        bg = seqset.background() if background is None else background
+        lls, expected = [], None
+        for _ in range(int(iterations)):
+            mats, expected, new_gamma, ll = self.em_step(mats, seqset, model, gamma, scale, pseudocount, bg)
+            lls.append(ll)
+            if new_gamma is not None:
+                gamma = np.clip(new_gamma, 1e-6, 1.0)
+        sums = self.scan_sum_set(mats, seqset, scale)
+        lls.append(_em_likelihood(sums, posterior_gains(sums, model, gamma), model, gamma)[0])
+        lls = np.asarray(lls, dtype=np.float64)
+        return (mats, lls, expected) if return_counts else (mats, lls)
 
     def _variant_args(self, batch: "MotifBatch", seqset: "StripedSequenceSet", records, positions, alts) -> np.ndarray:
         """The ``lm_hip_variant`` list of a call: records and positions as ``_u64_array`` takes them, ``alts`` symbol indices
@@ -1434,24 +1504,7 @@ class CountMatrix:
 
     def _to_freq(self, pseudocount: Union[None, float, Dict[str, float]]) -> np.ndarray:
         """pwm/mod.rs:240-258 ``to_freq(pseudo)`` in f32."""
-        k = self.data.shape[1]
-        f32 = np.float32
-        if pseudocount is None:
-            pseudo = np.zeros(k, dtype=f32)
-        elif isinstance(pseudocount, dict):
-            pseudo = _dict_to_rows({a: [b] for a, b in pseudocount.items()}, self.protein, f32)[0]
-        else:  # abc.rs:558-573: every symbol but the default one
-            pseudo = np.full(k, f32(pseudocount), dtype=f32)
-            pseudo[k - 1] = 0
-        out = np.zeros((len(self), k), dtype=f32)
-        for i in range(len(self)):
-            row = (self.data[i].astype(f32) + pseudo).astype(f32)  # pwm/mod.rs:249-251
-            total = f32(0)
-            for x in row:                                            # :252 sequential f32 sum
-                total = f32(total + x)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                out[i] = (row / total).astype(f32)                   # :253-255
-        return out
+        return _counts_to_freq(self.data, pseudocount, self.protein)
 
     def normalize(self, pseudocount: Union[None, float, Dict[str, float]] = None) -> "WeightMatrix":
         """lib.rs:501-526: ``to_freq(pseudo).to_weight(None)`` in f32."""
@@ -1469,21 +1522,108 @@ class CountMatrix:
         frequencies or an array of ``k`` of them (e.g. ``background_from_counts``); ``None`` is the uniform background, and
         the result is then ``normalize(pseudocount).log_odds()`` bit for bit.  This is NOT ``log_odds(background=...)``, the
         reference's ``rescale`` (pwm/mod.rs:471-492), which makes the default symbol's column ``0 * (0 / 0) = NaN``."""
-        f32 = np.float32
-        freq = self._to_freq(pseudocount)
-        k = freq.shape[1]
-        if background is None:
-            bg = uniform_background(k)
-        elif isinstance(background, dict):
-            bg = _dict_to_rows({a: [b] for a, b in background.items()}, self.protein, f32)[0]
-        else:
-            bg = np.array(background, dtype=f32)
-            if bg.shape != (k,):
-                raise ValueError(f"a background of {k} frequencies is needed")
+        return _freq_to_scoring(self._to_freq(pseudocount), background, self.protein)
+
+
+def _counts_to_freq(counts: np.ndarray, pseudocount: Union[None, float, Dict[str, float]], protein: bool) -> np.ndarray:
+    """``to_freq(pseudo)`` (pwm/mod.rs:240-258) in f32 of an ``(M, K)`` table of counts: the u32 counts of a ``CountMatrix``
+    and the float64 expected counts of ``Pipeline.expected_counts_set`` take the same steps (a count is converted to f32
+    first, exactly for integers below 2^24)."""
+    k = counts.shape[1]
+    f32 = np.float32
+    if pseudocount is None:
+        pseudo = np.zeros(k, dtype=f32)
+    elif isinstance(pseudocount, dict):
+        pseudo = _dict_to_rows({a: [b] for a, b in pseudocount.items()}, protein, f32)[0]
+    else:  # abc.rs:558-573: every symbol but the default one
+        pseudo = np.full(k, f32(pseudocount), dtype=f32)
+        pseudo[k - 1] = 0
+    out = np.zeros((len(counts), k), dtype=f32)
+    for i in range(len(counts)):
+        row = (counts[i].astype(f32) + pseudo).astype(f32)      # pwm/mod.rs:249-251
+        total = f32(0)
+        for x in row:                                            # :252 sequential f32 sum
+            total = f32(total + x)
         with np.errstate(divide="ignore", invalid="ignore"):
-            odds = (freq / np.where(bg == 0, f32(1), bg)).astype(f32)
-            out = np.where(bg == 0, f32(-np.inf), np.log2(odds, dtype=f32)).astype(f32)
-        return ScoringMatrix(out, bg, protein=self.protein)
+            out[i] = (row / total).astype(f32)                   # :253-255
+    return out
+
+
+def _freq_to_scoring(freq: np.ndarray, background: Union[None, Dict[str, float], np.ndarray], protein: bool) -> "ScoringMatrix":
+    """``into_scoring(background)`` (pwm/mod.rs:415-430) of f32 frequencies: ``log2(freq / f)`` in f32, ``-inf`` where the
+    background frequency ``f`` is zero."""
+    f32 = np.float32
+    k = freq.shape[1]
+    if background is None:
+        bg = uniform_background(k)
+    elif isinstance(background, dict):
+        bg = _dict_to_rows({a: [b] for a, b in background.items()}, protein, f32)[0]
+    else:
+        bg = np.array(background, dtype=f32)
+        if bg.shape != (k,):
+            raise ValueError(f"a background of {k} frequencies is needed")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        odds = (freq / np.where(bg == 0, f32(1), bg)).astype(f32)
+        out = np.where(bg == 0, f32(-np.inf), np.log2(odds, dtype=f32)).astype(f32)
+    return ScoringMatrix(out, bg, protein=protein)
+
+
+def expected_to_scoring(counts: np.ndarray, pseudocount: Union[None, float, Dict[str, float]] = None,
+                        background: Union[None, Dict[str, float], np.ndarray] = None, *, protein: bool = False) -> "ScoringMatrix":
+    """The M-step of motif EM: ``CountMatrix.to_scoring`` on an ``(M, K)`` table of float counts (the expected site counts of
+    ``Pipeline.expected_counts_set``), the same f32 arithmetic: integer-valued counts give the ``CountMatrix`` result bit
+    for bit."""
+    counts = np.asarray(counts, dtype=np.float64)
+    if counts.ndim != 2 or counts.shape[1] != _k(protein):
+        raise ValueError(f"expected counts: an (M, {_k(protein)}) table")
+    return _freq_to_scoring(_counts_to_freq(counts, pseudocount, protein), background, protein)
+
+
+def posterior_gains(sums: "SetSums", model: str = "oops", gamma=None) -> np.ndarray:
+    """The per-record gains that turn the odds of a window into its posterior (``Pipeline.expected_counts_set``), from the
+    total odds ``Z`` of ``Pipeline.scan_sum_set``, ``(motifs, records)`` float64:
+
+    ``"oops"``   one site per record: ``g = 1 / Z_r``;
+    ``"zoops"``  zero or one site per record, a site with prior probability ``gamma`` (one number, or one per motif, in
+                 (0, 1]): ``g = lambda_r / ((1 - gamma) + lambda_r * Z_r)``, ``lambda_r = gamma / windows_r``.
+
+    Cells of records without a window, or whose ``Z`` is 0 or not finite, get gain 0 (the record is switched off)."""
+    z = np.asarray(sums.sums, dtype=np.float64)
+    windows = np.asarray(sums.windows, dtype=np.float64)
+    ok = (windows > 0) & np.isfinite(z) & (z > 0)
+    zs, ws = np.where(ok, z, 1.0), np.where(ok, windows, 1.0)
+    with np.errstate(over="ignore", divide="ignore", invalid="ignore"):
+        if model == "oops":
+            g = 1.0 / zs
+        elif model == "zoops":
+            if gamma is None:
+                raise ValueError("zoops: gamma, the prior probability of a site in a record, is needed")
+            gm = np.asarray(gamma, dtype=np.float64)
+            gm = gm.reshape(-1, 1) if gm.ndim else gm
+            if not np.all((gm > 0) & (gm <= 1)):
+                raise ValueError("zoops: gamma lies in (0, 1]")
+            lam = gm / ws
+            g = lam / ((1.0 - gm) + lam * zs)
+        else:
+            raise ValueError(f"model {model!r}: 'oops' or 'zoops'")
+    return np.ascontiguousarray(np.where(ok & np.isfinite(g), g, 0.0), dtype=np.float64)
+
+
+def _em_likelihood(sums: "SetSums", gains: np.ndarray, model: str, gamma):
+    """``(log2-likelihood ratio per motif, new gamma per motif or None)`` of ``Pipeline.em_step`` from the total odds and the
+    gains made of them: over the records that are switched on, ``log2 Z_r`` (OOPS) or ``log2((1 - gamma) + lambda_r Z_r)``
+    (ZOOPS), and for ZOOPS the mean posterior mass ``g_r Z_r`` per record with a window."""
+    live = gains > 0
+    z = np.where(live, sums.sums, 1.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if model == "oops":
+            return np.log2(z).sum(axis=1), None
+        gm = np.asarray(gamma, dtype=np.float64)
+        gm = gm.reshape(-1, 1) if gm.ndim else gm
+        lam = gm / np.maximum(sums.windows, 1)
+        ll = np.where(live, np.log2((1.0 - gm) + lam * z), 0.0).sum(axis=1)
+        has = np.maximum((sums.windows > 0).sum(axis=1), 1)
+        return ll, np.minimum(np.where(live, gains * z, 0.0).sum(axis=1) / has, 1.0)
 
 
 def uniform_background(k: int) -> np.ndarray:
@@ -1841,6 +1981,22 @@ class SetSums:
         """log2 of the total odds: -inf where the sum is 0."""
         with np.errstate(divide="ignore"):
             return np.log2(self.sums)
+
+
+class SetExpectedCounts:
+    """The result of ``Pipeline.expected_counts_set``: ``counts`` -- per motif an ``(M_i, K)`` float64 table of expected
+    symbol counts, exact multiples of ``2 ** -frac_bits`` --, ``frac_bits`` -- the fixed point of the set -- and ``kernel``
+    -- the kernel that ran last for the call ("" when nothing ran)."""
+
+    def __init__(self, counts: List[np.ndarray], frac_bits: int, kernel: str = ""):
+        self.counts, self.frac_bits, self.kernel = counts, frac_bits, kernel
+
+    def __len__(self) -> int:
+        return len(self.counts)
+
+    def quanta(self) -> List[np.ndarray]:
+        """The tables as the integers the device summed: ``counts * 2 ** frac_bits``, int64."""
+        return [np.ldexp(c, self.frac_bits).astype(np.int64) for c in self.counts]
 
 
 VARIANT_DTYPE = np.dtype({"names": ["record", "position", "alt"], "formats": [np.uint64, np.uint64, np.uint8],

@@ -36,6 +36,12 @@ how many of them reach the motif's threshold (``Pipeline.scan_count_set``: no hi
 record, the sum of ``2 ** score`` over them (``Pipeline.scan_sum_set``: no hit list is made; the scores are log2 odds) and
 ``log2(sum_odds / windows)``, both written with ``repr``.  Thresholds play no part; it excludes ``--best``, ``--counts``,
 ``--variants``, ``--matched`` and ``--site-matrices``.
+``--refine N --refined PATH`` refines every motif on the input before the scan: N iterations of EM on the resident set
+(``Pipeline.refine``: per iteration the total odds per record, then the expected site counts of all windows, both on the
+device, then new matrices; ``--refine-model oops`` -- one site per record, the default -- or ``zoops``), from the forward
+matrices as loaded and against the set's own background.  ``PATH`` receives one JASPAR-2016 record per motif: the expected
+site counts of the last iteration, rounded to integers.  The input has to fit ONE resident set (``--batch-bases``).  The
+scan then proceeds with the matrices as loaded: no other output changes.
 ``--pvalues device`` (the default) builds the score distributions of all motifs on the device
 (``Pipeline.score_distributions``): the thresholds of ``-P`` come from one call, and the ``pvalue`` column of a set from one
 call per strand on the set's hits.  ``--pvalues host`` is the per-motif, per-hit host code of ``dist.py``; the TSV is the
@@ -85,6 +91,7 @@ from __future__ import annotations
 import argparse
 import contextlib
 import gzip
+import itertools
 import math
 import sys
 from typing import BinaryIO, Iterator, List, Optional, Sequence, TextIO, Tuple
@@ -384,6 +391,15 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--regions", metavar="BED",
                     help="scan regions of the FASTA records instead of the records: a BED file (chrom, 0-based start, end, "
                          "optional name and strand), cut out of each resident set on the device")
+    ap.add_argument("--refine", type=int, metavar="N",
+                    help="before scanning, refine every motif on the input by N iterations of EM on the device (expected site "
+                         "counts of all windows, then new matrices) and write the result to --refined; the input has to fit one "
+                         "resident set (--batch-bases); the scan itself uses the matrices as loaded")
+    ap.add_argument("--refine-model", choices=("oops", "zoops"), default="oops",
+                    help="with --refine: one site per record (oops, default) or zero or one (zoops)")
+    ap.add_argument("--refined", metavar="PATH",
+                    help="with --refine: the JASPAR-2016 file of the refined motifs, per motif the expected site counts of the last "
+                         "iteration rounded to integers")
     resize = ap.add_mutually_exclusive_group()
     resize.add_argument("--flank", type=int, metavar="N", help="with --regions: extend every region by N symbols on both sides")
     resize.add_argument("--resize", type=int, metavar="W", help="with --regions: a window of W symbols centred on every region's midpoint")
@@ -402,6 +418,12 @@ def log2_mean_odds(total: float, windows: int) -> float:
     """``log2(total / windows)`` of a ``--sum-odds`` line: -inf for a total of 0, +inf for one of +inf."""
     mean = total / windows
     return math.log2(mean) if 0.0 < mean < math.inf else (-math.inf if mean == 0.0 else mean)
+
+
+def refined_counts(expected: np.ndarray) -> CountMatrix:
+    """The count matrix ``--refined`` writes for a motif: its expected site counts rounded to the nearest integer (ties to
+    even), the form the JASPAR-2016 format holds."""
+    return CountMatrix(np.rint(expected).astype(np.uint32))
 
 
 def hit_pvalues(dists, motif: np.ndarray, score: np.ndarray) -> np.ndarray:
@@ -443,6 +465,10 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         ap.error("--regions excludes --variants: variant coordinates would have to be remapped to the regions")
     if (args.flank is not None and args.flank < 0) or (args.resize is not None and args.resize < 0):
         ap.error("--flank and --resize take a non-negative number of symbols")
+    if (args.refine is None) != (args.refined is None):
+        ap.error("--refine and --refined go together")
+    if args.refine is not None and args.refine < 1:
+        ap.error("--refine takes a positive number of iterations")
     bed_by_chrom: dict = {}
     if args.regions:
         try:
@@ -544,6 +570,19 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
         strands.append(("-", [p.reverse_complement() for p in direct]))
     max_m = max(lengths, default=0)
     batches = [(strand, pli.prepare_batch(pssms, thresholds)) for strand, pssms in strands]
+    if args.refine is not None:
+        resident = list(itertools.islice(sets(), 2))
+        if len(resident) > 1:
+            ap.error("--refine works on one resident set: the input is larger than --batch-bases")
+        refined = [r.matrix for r in records]
+        if resident and records:
+            _, _, seqset = resident[0]
+            seqset.configure_wrap(max_m)
+            _, _, expected = pli.refine(direct, seqset, args.refine, model=args.refine_model, return_counts=True)
+            refined = [refined_counts(e) for e in expected.counts]
+        lmio.write([lmio.Record(r.id, r.description, m) for r, m in zip(records, refined)], args.refined)
+        print(f"Wrote {len(refined)} refined matrices to {args.refined}")
+        del resident
     if variants is not None:
         by_name: dict = {}
         for vi, (_, name, _, _, _) in enumerate(variants):
